@@ -25,22 +25,25 @@ Order of a run (whatever K and W are, so that a 20-step line and a 2000-step lin
   3. barrier + synchronize, `run K`, barrier + synchronize.  `value` = K / Loop time of that run, the metric exactly
      as the reference prints it (src/finish.cpp:124-145: the timer starts after Verlet::setup, src/run.cpp:178-186),
      MAX over ranks; the wall clock around the whole `run K` (setup included) is reported as `wall_s` / `value_wall`;
-  4. the three LE firings timed on their own (`le_firing`): the steps ...001-...010 of the next period (extrusion at
-     ...001, ex_unload at ...002, ex_load at ...003, each followed by the reneighboring it forces) against ten
-     ordinary steps, so a short window that holds no firing still reports what a firing costs;
-  5. only now is the state copied out for the CPU baseline (the copy idles the GPU; nothing timed follows it).
+  4. `--dump-outputs DIR`: the state the last timed step left (see dump_outputs) is written to DIR as .npy files;
+  5. `--full` only: the three LE firings timed on their own (`le_firing`): the steps ...001-...010 of the next period
+     (extrusion at ...001, ex_unload at ...002, ex_load at ...003, each followed by the reneighboring it forces) against
+     ten ordinary steps, so a short window that holds no firing still reports what a firing costs;
+  6. `--full` only: the state is copied out for the CPU baseline (the copy idles the GPU; nothing timed follows it).
+A plain run (no `--full`) stops after 4 and reports `le_firing` and `cpu_baseline` as null.
 
 Extra objects on the JSON line:
   roofline     — the fused step kernel k_step: algorithmic bytes (132*N + 4*(F + 2*B), F = stored full-list entries, B = bonds;
                  DESIGN.md §3) / mean kernel duration from HIP events recorded on the launch stream inside the
                  engine over the timed region (every launch when K <= 64, every 16th otherwise), vs the 8 TB/s peak.
-  cpu_baseline — the CPU oracle (oracle/le_oracle.c, a serial port of the reference path) on 1 host core, on a
+  cpu_baseline — (`--full`) the CPU oracle (oracle/le_oracle.c, a serial port of the reference path) on 1 host core, on a
                  bounded sample of the same system from the state (positions, velocities, bond topology with its
                  extruders) the GPU run ended in; reported, not the target.
 """
 import argparse
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
@@ -94,6 +97,40 @@ def bonds_by_tag(lmp):
     return np.stack([bt[keep], own[keep], ba[keep]], axis=1).astype(np.int32)
 
 
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def dump_outputs(lmp, outdir, write):
+    """What a caller of `run K` gets back, as DIR/<name>.npy: per bead (rows = beads in ascending tag order) tag, x, v,
+    image, type and the bond table (bond_partner / bond_type, each bead's bonds sorted by partner tag, empty slots 0);
+    thermo = step temp epair emol press bonds of the last timed step.  Float64 for x, v, tag and thermo, float32 for the
+    other integer-valued arrays (exact below 2^24).  If all beads do not fit in DUMP_BUDGET_BYTES, the rows are a fixed
+    sample (seed 0, depends on the bead count only).  gather() is collective: every rank calls this, `write` on one."""
+    n = lmp.get_natoms()
+    x, v, image, typ = lmp.gather("x"), lmp.gather("v"), lmp.gather("image"), lmp.gather("type")
+    nb, bt, ba = lmp.gather("num_bond"), lmp.gather("bond_type").reshape(n, -1), lmp.gather("bond_atom").reshape(n, -1)
+    thermo = np.array([lmp.get_thermo(k) for k in ("step", "temp", "epair", "emol", "press", "bonds")], dtype=np.float64)
+    if not write:
+        return
+    w = ba.shape[1]
+    per_bead = 8 + 24 + 24 + 12 + 4 + 8 * w
+    rows = np.arange(n)
+    if n * per_bead > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, size=DUMP_BUDGET_BYTES // per_bead, replace=False))
+    live = np.arange(w)[None, :] < nb[rows, None]
+    key = np.where(live, ba[rows].astype(np.int64) * (int(bt.max()) + 1) + bt[rows], np.iinfo(np.int64).max)
+    order = np.argsort(key, axis=1, kind="stable")
+    live = np.take_along_axis(live, order, axis=1)
+    out = {"tag": (rows + 1).astype(np.float64), "x": x[rows], "v": v[rows], "image": image[rows].astype(np.float32),
+           "type": typ[rows].astype(np.float32),
+           "bond_partner": np.where(live, np.take_along_axis(ba[rows], order, axis=1), 0).astype(np.float32),
+           "bond_type": np.where(live, np.take_along_axis(bt[rows], order, axis=1), 0).astype(np.float32),
+           "thermo": thermo}
+    os.makedirs(outdir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def self_launch(n):
     """`python bench.py --gpus N` without a launcher: be the launcher.  N children, one per GPU, each a fresh process (the
     parent never imports torch or touches HIP, and no process that has is ever re-exec'ed); rank 0 inherits stdout, so its
@@ -138,7 +175,12 @@ def main():
     ap.add_argument("--workload", default="walk1m", choices=sorted(WORKLOADS))
     ap.add_argument("--pre-roll", type=int, default=-1,
                     help="untimed steps before the warm-up (default: past three firings of every LE fix)")
-    ap.add_argument("--cpu-steps", type=int, default=-1, help="oracle sample length (0 = skip the CPU baseline)")
+    ap.add_argument("--cpu-steps", type=int, default=-1,
+                    help="with --full: oracle sample length (0 = skip the CPU baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the LE firings on their own (le_firing) and run the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the last timed step left to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -279,10 +321,12 @@ def main():
     nbonds = lmp.get_thermo("bonds")
     nlocal = lmp.stat("nlocal")
     sections = {k: round(lmp.stat("time_" + k), 6) for k in ("pair", "neigh", "comm", "modify", "output", "other")}
+    if args.dump_outputs:
+        dump_outputs(lmp, args.dump_outputs, write=(rank == 0))
 
-    # ---- 4. what a firing of the three LE fixes costs (untimed for `value`) ----
+    # ---- 5. (--full) what a firing of the three LE fixes costs (untimed for `value`) ----
     le_firing = None
-    if period >= 100:
+    if args.full and period >= 100:
         now = int(lmp.get_thermo("step"))
         to_boundary = (period - now % period) % period
         if to_boundary:
@@ -321,12 +365,12 @@ def main():
                 "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(kms, 5),
                 "launches_timed": klaunches}
 
-    # ---- 5. CPU baseline: the oracle on a bounded sample, rank 0 at N=1 only ----
+    # ---- 6. (--full) CPU baseline: the oracle on a bounded sample, rank 0 at N=1 only ----
     cpu = None
     cpu_steps = args.cpu_steps
     if cpu_steps < 0:
         cpu_steps = max(10, int(4.0e6 * 15 / nbeads)) if nbeads >= 100000 else 2000
-    if rank == 0 and world == 1 and cpu_steps > 0:
+    if args.full and rank == 0 and world == 1 and cpu_steps > 0:
         from systems import OracleScript
         s2 = dict(sysd)
         s2["x"], s2["v"], s2["image"] = lmp.gather("x"), lmp.gather("v"), lmp.gather("image")
@@ -392,6 +436,7 @@ def main():
         }
         os.write(result_fd, (json.dumps(out) + "\n").encode())
     lmp.close()
+    shutil.rmtree(tmp, ignore_errors=True)
     if world > 1:
         dist.destroy_process_group()
 

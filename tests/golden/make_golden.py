@@ -27,6 +27,7 @@ import json
 import os
 import re
 import sys
+import zipfile
 
 import numpy as np
 
@@ -68,6 +69,14 @@ def parse_data(path):
         else:
             sections[cur].append(ln.split())
     return hdr, sections
+
+
+def savez_lzma(path, **arrays):
+    """np.savez_compressed with LZMA instead of deflate (keeps chain32k.npz under 1 MiB); np.load reads it as is."""
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for name, arr in arrays.items():
+            with z.open(name + ".npy", "w") as fh:
+                np.lib.format.write_array(fh, np.asanyarray(arr), allow_pickle=False)
 
 
 def yaml_block(text, key):
@@ -149,7 +158,7 @@ def main():
     vel = np.zeros((len(tag), 3))
     vel[vtag - 1] = v[:, 1:4].astype(np.float64)
     b = np.array(sec["Bonds"], dtype=np.int32)
-    np.savez_compressed(
+    savez_lzma(
         OUT + "/chain32k.npz",
         box=np.array([hdr["x"], hdr["y"], hdr["z"]], dtype=np.float64),
         tag=tag, mol=a[:, 1].astype(np.int32), type=a[:, 2].astype(np.int32),

@@ -1,8 +1,10 @@
 """GPU edge cases of the script layer + kernels: non-uniform pair coefficients (table path), special_bonds
 lj 1 1 1 (no exclusions), ex_load type conversion, error propagation (Bad FENE bond), several runs with
-thermo fix keywords, write_data round trip, the lmp_le command-line driver."""
+thermo fix keywords, write_data round trip, the lmp_le command-line driver, bench.py --dump-outputs."""
+import json
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -354,3 +356,29 @@ def test_neighbor_table_overflow_is_recovered(tmp_path, monkeypatch, n):
     p = run_product(script, s, tmp_path)
     assert relerr(p.gather("x"), o.x()) < 1e-9 and relerr(p.gather("v"), o.v()) < 1e-8
     assert p.stat("neigh_builds") == o.neigh_builds() and p.stat("neigh_pairs") == 2 * o.neigh_pairs()
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run (no --full: no le_firing, no cpu_baseline) writes the state its last
+    timed step left - every bead of the 32k system in tag order, float32 / float64 only, thermo at step pre-roll +
+    warm-up + steps, each interior bead bonded to its chain neighbours."""
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--workload", "chain32k", "--pre-roll", "0", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.split("\n") if ln.strip()]
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["steps"] == 20 and line["ms_per_step"] > 0 and line["le_firing"] is None and line["cpu_baseline"] is None
+    d = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert sorted(d) == ["bond_partner", "bond_type", "image", "tag", "thermo", "type", "v", "x"]
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert sum(os.path.getsize(str(out / f)) for f in os.listdir(str(out))) < 64e6
+    n = 32000
+    assert np.array_equal(d["tag"], np.arange(1, n + 1)) and d["x"].shape == d["v"].shape == (n, 3)
+    assert np.isfinite(d["x"]).all() and np.isfinite(d["v"]).all()
+    assert d["thermo"][0] == 25 and d["thermo"][5] >= n - 1
+    partners = d["bond_partner"].astype(np.int64)
+    tags = np.arange(2, n).reshape(-1, 1)
+    assert ((partners[1:-1] == tags - 1).any(axis=1) & (partners[1:-1] == tags + 1).any(axis=1)).all()
