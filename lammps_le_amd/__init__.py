@@ -23,6 +23,13 @@ class LammpsError(Exception):
     pass
 
 
+# data types of lammps_extract_global_datatype / lammps_extract_atom_datatype (src/library.h:47-55) and the style / type
+# selectors of lammps_extract_compute (:61-78)
+LAMMPS_INT, LAMMPS_INT_2D, LAMMPS_DOUBLE, LAMMPS_DOUBLE_2D, LAMMPS_INT64, LAMMPS_INT64_2D, LAMMPS_STRING = range(7)
+LMP_STYLE_GLOBAL, LMP_STYLE_ATOM, LMP_STYLE_LOCAL = range(3)
+LMP_TYPE_SCALAR, LMP_TYPE_VECTOR, LMP_TYPE_ARRAY, LMP_SIZE_VECTOR, LMP_SIZE_ROWS, LMP_SIZE_COLS = range(6)
+
+
 def library_path():
     return _SO
 
@@ -61,6 +68,23 @@ def _load():
     lib.lammps_has_style.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
     lib.lammps_le_stat.argtypes = [C.c_void_p, C.c_char_p]
     lib.lammps_le_stat.restype = C.c_double
+    for fn in ("lammps_gather_atoms_subset", "lammps_scatter_atoms_subset", "lammps_gather_subset", "lammps_scatter_subset"):
+        getattr(lib, fn).argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]
+    for fn in ("lammps_gather_atoms_concat", "lammps_gather_concat", "lammps_gather", "lammps_scatter"):
+        getattr(lib, fn).argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
+    lib.lammps_extract_compute.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
+    lib.lammps_extract_compute.restype = C.c_void_p
+    lib.lammps_extract_variable.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    lib.lammps_extract_variable.restype = C.c_void_p
+    lib.lammps_extract_variable_datatype.argtypes = [C.c_void_p, C.c_char_p]
+    lib.lammps_set_variable.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    lib.lammps_set_variable.restype = C.c_int
+    lib.lammps_has_id.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
+    lib.lammps_id_count.argtypes = [C.c_void_p, C.c_char_p]
+    lib.lammps_id_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
+    lib.lammps_force_timeout.argtypes = [C.c_void_p]
+    lib.lammps_style_count.argtypes = [C.c_void_p, C.c_char_p]
+    lib.lammps_style_name.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int]
     return lib
 
 
@@ -196,6 +220,129 @@ class lammps(object):
                 if a2[i, m] == i + 1:
                     out.add((int(at[i, m]), int(min(a1[i, m], a3[i, m])), int(a2[i, m]), int(max(a1[i, m], a3[i, m]))))
         return out
+
+    # -- ID-addressed access (python/lammps.py gather_atoms_subset / scatter_atoms_subset): only the requested rows travel --
+    def gather_atoms_subset(self, name, type, count, ndata, ids):
+        """As python/lammps.py: a ctypes array of ndata*count values in the order of `ids`."""
+        cids = (C.c_int * ndata)(*[int(i) for i in ids[:ndata]])
+        data = ((C.c_double if type == 1 else C.c_int) * (ndata * count))()
+        self.lib.lammps_gather_atoms_subset(self.lmp, name.encode(), type, count, ndata, cids, data)
+        self._check()
+        return data
+
+    def scatter_atoms_subset(self, name, type, count, ndata, ids, data):
+        cids = (C.c_int * ndata)(*[int(i) for i in ids[:ndata]])
+        self.lib.lammps_scatter_atoms_subset(self.lmp, name.encode(), type, count, ndata, cids, data)
+        self._check()
+
+    def gather_atoms_concat(self, name, type, count):
+        """As python/lammps.py: every atom in the engine's local order (gather_atoms_concat("id", 0, 1) gives that order)."""
+        n = self.get_natoms()
+        data = ((C.c_double if type == 1 else C.c_int) * (n * count))()
+        self.lib.lammps_gather_atoms_concat(self.lmp, name.encode(), type, count, data)
+        self._check()
+        return data
+
+    def _shape(self, name):
+        """(type, count) of a per-atom name, as gather() uses them."""
+        if name in ("x", "v", "f"):
+            return 1, 3
+        if name in ("bond_type", "bond_atom"):
+            return 0, self.extract_setting("bond_per_atom")
+        if name == "special":
+            return 0, self.extract_setting("maxspecial")
+        if name in ("angle_type", "angle_atom1", "angle_atom2", "angle_atom3"):
+            return 0, self.extract_setting("angle_per_atom")
+        return 0, {"image": 3, "nspecial": 3}.get(name, 1)
+
+    def gather_ids(self, name, ids):
+        """numpy rows of `name` for the atom IDs `ids` (any order, repeats allowed): shape (len(ids), count), or
+        (len(ids),) for one value per atom."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        type, count = self._shape(name)
+        out = np.zeros((len(ids), count), dtype=np.float64 if type == 1 else np.int32)
+        self.lib.lammps_gather_atoms_subset(self.lmp, name.encode(), type, count, len(ids),
+                                            ids.ctypes.data_as(C.POINTER(C.c_int)), out.ctypes.data_as(C.c_void_p))
+        self._check()
+        return out[:, 0] if count == 1 else out
+
+    def scatter_ids(self, name, ids, arr):
+        """Set `name` of the atoms `ids` from the rows of `arr` (x v f: (K, 3); image: (K, 3) unpacked; type: (K,))."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32).ravel()
+        type = 1 if name in ("x", "v", "f") else 0
+        arr = np.ascontiguousarray(arr, dtype=np.float64 if type == 1 else np.int32).reshape(len(ids), -1)
+        self.lib.lammps_scatter_atoms_subset(self.lmp, name.encode(), type, arr.shape[1], len(ids),
+                                             ids.ctypes.data_as(C.POINTER(C.c_int)), arr.ctypes.data_as(C.c_void_p))
+        self._check()
+
+    # -- computes and variables (python/lammps.py extract_compute / extract_variable / set_variable) --
+    def extract_compute(self, cid, style, type):
+        """style 0 global / 2 local; type 0 scalar, 1 vector, 2 array, 3 size vector, 4 rows, 5 cols (LMP_* constants).
+        Returns a float, a list of floats, a list of rows, or an int; None where the compute has no such data."""
+        p = self.lib.lammps_extract_compute(self.lmp, cid.encode(), style, type)
+        self._check()
+        if not p:
+            return None
+        if type in (3, 4, 5) or (style == 2 and type == 0):
+            return C.cast(p, C.POINTER(C.c_int))[0]
+        if type == 0:
+            return C.cast(p, C.POINTER(C.c_double))[0]
+        if style == 0:
+            n = C.cast(self.lib.lammps_extract_compute(self.lmp, cid.encode(), style, 3), C.POINTER(C.c_int))[0]
+            return list(C.cast(p, C.POINTER(C.c_double))[:n])
+        rows = C.cast(self.lib.lammps_extract_compute(self.lmp, cid.encode(), 2, 4), C.POINTER(C.c_int))[0]
+        if type == 1:
+            return list(C.cast(p, C.POINTER(C.c_double))[:rows])
+        cols = C.cast(self.lib.lammps_extract_compute(self.lmp, cid.encode(), 2, 5), C.POINTER(C.c_int))[0]
+        pp = C.cast(p, C.POINTER(C.POINTER(C.c_double)))
+        return [list(pp[r][:cols]) for r in range(rows)]
+
+    def extract_variable(self, name, group=None, vartype=None):
+        """equal-style: float; index / loop / string: str; unknown: None.  (The style comes from the engine, so `vartype`
+        of python/lammps.py is accepted and not needed.)"""
+        style = self.lib.lammps_extract_variable_datatype(self.lmp, name.encode())
+        if style < 0:
+            return None
+        p = self.lib.lammps_extract_variable(self.lmp, name.encode(), group.encode() if group else None)
+        self._check()
+        if not p:
+            return None
+        if style == 0:
+            val = C.cast(p, C.POINTER(C.c_double))[0]
+            self.lib.lammps_free(p)
+            return val
+        return C.cast(p, C.c_char_p).value.decode()
+
+    def set_variable(self, name, value):
+        """Set a string-style variable; returns 0, or -1 if there is no string-style variable of that name."""
+        r = self.lib.lammps_set_variable(self.lmp, name.encode(), str(value).encode())
+        self._check()
+        return r
+
+    def has_id(self, category, name):
+        return self.lib.lammps_has_id(self.lmp, category.encode(), name.encode()) != 0
+
+    def id_count(self, category):
+        return self.lib.lammps_id_count(self.lmp, category.encode())
+
+    def available_ids(self, category):
+        buf = C.create_string_buffer(256)
+        out = []
+        for i in range(self.id_count(category)):
+            self.lib.lammps_id_name(self.lmp, category.encode(), i, buf, 256)
+            out.append(buf.value.decode())
+        return out
+
+    def available_styles(self, category):
+        buf = C.create_string_buffer(256)
+        out = []
+        for i in range(self.lib.lammps_style_count(self.lmp, category.encode())):
+            self.lib.lammps_style_name(self.lmp, category.encode(), i, buf, 256)
+            out.append(buf.value.decode())
+        return out
+
+    def force_timeout(self):
+        self.lib.lammps_force_timeout(self.lmp)
 
     def has_style(self, category, name):
         return self.lib.lammps_has_style(self.lmp, category.encode(), name.encode()) != 0

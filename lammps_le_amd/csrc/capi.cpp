@@ -1,6 +1,9 @@
 // capi.cpp — extern "C" boundary (include/lammps_le.h): the reference's library.h subset for this path.
 // Behaviour follows src/library.cpp; every entry point catches LammpsError and records it
 // (the reference does the same when built with LAMMPS_EXCEPTIONS, src/library.cpp BEGIN_CAPTURE/END_CAPTURE).
+#include <sys/utsname.h>
+
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -171,50 +174,570 @@ static int topo_width(Engine *e, const std::string &k) {
   return 0;
 }
 
+// the whole-system forms, ordered by atom ID (fn: the entry point named in error messages)
+static void gather_atoms_impl(Engine *e, const char *fn, const char *name, int type, int count, void *data) {
+  e->download();
+  std::string k = name;
+  int n = e->natoms;
+  if (type == 1) {
+    std::vector<double> *src = (k == "x") ? &e->x : (k == "v") ? &e->v : (k == "f") ? &e->f : nullptr;
+    if (!src || count != 3) throw LammpsError(std::string(fn) + ": unknown property name " + k);
+    memcpy(data, src->data(), 3 * (size_t)n * sizeof(double));
+  } else {
+    int *out = (int *)data;
+    if (k == "type" && count == 1) memcpy(out, e->type.data(), n * sizeof(int));
+    else if (k == "id" && count == 1) for (int i = 0; i < n; i++) out[i] = i + 1;
+    else if (k == "mask" && count == 1) for (int i = 0; i < n; i++) out[i] = (int)e->gmask.size() == n ? (e->gmask[i] | 1) : 1;
+    else if (k == "molecule" && count == 1) memcpy(out, e->molecule.data(), n * sizeof(int));
+    else if (k == "image" && count == 3) memcpy(out, e->image.data(), 3 * (size_t)n * sizeof(int));
+    else if (k == "image" && count == 1)
+      for (int i = 0; i < n; i++) out[i] = lammps_encode_image_flags(e->image[3 * i], e->image[3 * i + 1], e->image[3 * i + 2]);
+    else if (topo_width(e, k) == count && count > 0) {
+      const std::vector<int> &src = (k == "num_bond") ? e->num_bond : (k == "bond_type") ? e->bond_type :
+                                    (k == "bond_atom") ? e->bond_atom : (k == "nspecial") ? e->nspecial :
+                                    (k == "num_angle") ? e->num_angle : (k == "angle_type") ? e->angle_type :
+                                    (k == "angle_atom1") ? e->angle_a1 : (k == "angle_atom2") ? e->angle_a2 :
+                                    (k == "angle_atom3") ? e->angle_a3 : e->special;
+      memcpy(out, src.data(), (size_t)n * count * sizeof(int));
+    } else throw LammpsError(std::string(fn) + ": unknown property name " + k);
+  }
+}
+
+static void scatter_atoms_impl(Engine *e, const char *fn, const char *name, int type, int count, void *data) {
+  e->download();
+  std::string k = name;
+  int n = e->natoms;
+  if (type == 1 && count == 3 && (k == "x" || k == "v" || k == "f")) {
+    std::vector<double> &dst = (k == "x") ? e->x : (k == "v") ? e->v : e->f;
+    memcpy(dst.data(), data, 3 * (size_t)n * sizeof(double));
+  } else if (type == 0 && count == 1 && k == "type") memcpy(e->type.data(), data, n * sizeof(int));
+  else if (type == 0 && count == 3 && k == "image") memcpy(e->image.data(), data, 3 * (size_t)n * sizeof(int));
+  else throw LammpsError(std::string(fn) + ": unknown property name " + k);
+  e->dev_current = false;   // next run re-uploads
+}
 void lammps_gather_atoms(void *handle, char *name, int type, int count, void *data) {
-  BEGIN_CAPTURE
-    e->download();
-    std::string k = name;
-    int n = e->natoms;
-    if (type == 1) {
-      std::vector<double> *src = (k == "x") ? &e->x : (k == "v") ? &e->v : (k == "f") ? &e->f : nullptr;
-      if (!src || count != 3) throw LammpsError("lammps_gather_atoms: unknown property name " + k);
-      memcpy(data, src->data(), 3 * (size_t)n * sizeof(double));
-    } else {
-      int *out = (int *)data;
-      if (k == "type" && count == 1) memcpy(out, e->type.data(), n * sizeof(int));
-      else if (k == "id" && count == 1) for (int i = 0; i < n; i++) out[i] = i + 1;
-      else if (k == "mask" && count == 1) for (int i = 0; i < n; i++) out[i] = (int)e->gmask.size() == n ? (e->gmask[i] | 1) : 1;
-      else if (k == "molecule" && count == 1) memcpy(out, e->molecule.data(), n * sizeof(int));
-      else if (k == "image" && count == 3) memcpy(out, e->image.data(), 3 * (size_t)n * sizeof(int));
-      else if (k == "image" && count == 1)
-        for (int i = 0; i < n; i++) out[i] = lammps_encode_image_flags(e->image[3 * i], e->image[3 * i + 1], e->image[3 * i + 2]);
-      else if (topo_width(e, k) == count && count > 0) {
-        const std::vector<int> &src = (k == "num_bond") ? e->num_bond : (k == "bond_type") ? e->bond_type :
-                                      (k == "bond_atom") ? e->bond_atom : (k == "nspecial") ? e->nspecial :
-                                      (k == "num_angle") ? e->num_angle : (k == "angle_type") ? e->angle_type :
-                                      (k == "angle_atom1") ? e->angle_a1 : (k == "angle_atom2") ? e->angle_a2 :
-                                      (k == "angle_atom3") ? e->angle_a3 : e->special;
-        memcpy(out, src.data(), (size_t)n * count * sizeof(int));
-      } else throw LammpsError("lammps_gather_atoms: unknown property name " + k);
+  BEGIN_CAPTURE gather_atoms_impl(e, "lammps_gather_atoms", name, type, count, data); END_CAPTURE
+}
+void lammps_scatter_atoms(void *handle, char *name, int type, int count, void *data) {
+  BEGIN_CAPTURE scatter_atoms_impl(e, "lammps_scatter_atoms", name, type, count, data); END_CAPTURE
+}
+
+
+// ---- ID-addressed subsets (src/library.cpp:2225-2363 gather_atoms_subset, :2482-2614 scatter_atoms_subset) ----
+// While the device holds the newer state, the K requested rows move through kernels_capi.hip and nothing downloads the system;
+// otherwise (before the first run, after a whole-system scatter) the host copies in tag order are the state and serve the call.
+static bool device_is_newer(Engine *e) { return e->dev && e->dev_current && e->dev->pos && !e->host_current; }
+
+static void check_ids(Engine *e, const char *fn, int ndata, const int *ids) {
+  if (ndata < 0) throw LammpsError(std::string(fn) + ": invalid number of atoms");
+  for (int i = 0; i < ndata; i++)
+    if (ids[i] < 1 || ids[i] > e->natoms) throw LammpsError(std::string(fn) + ": unknown atom ID " + std::to_string(ids[i]));
+}
+
+// the int table a subset row of a topology name comes from (host copy or device table, both row t-1 / t of width count)
+static const std::vector<int> *host_topo(Engine *e, const std::string &k) {
+  return (k == "num_bond") ? &e->num_bond : (k == "bond_type") ? &e->bond_type : (k == "bond_atom") ? &e->bond_atom :
+         (k == "nspecial") ? &e->nspecial : (k == "special") ? &e->special : (k == "num_angle") ? &e->num_angle :
+         (k == "angle_type") ? &e->angle_type : (k == "angle_atom1") ? &e->angle_a1 : (k == "angle_atom2") ? &e->angle_a2 :
+         (k == "angle_atom3") ? &e->angle_a3 : nullptr;
+}
+static const int *dev_topo(DeviceState &d, const std::string &k) {
+  return (k == "num_bond") ? d.num_bond : (k == "bond_type") ? d.bond_type : (k == "bond_atom") ? d.bond_atom :
+         (k == "nspecial") ? d.nspecial : (k == "special") ? d.special : (k == "num_angle") ? d.num_angle :
+         (k == "angle_type") ? d.angle_type : (k == "angle_atom1") ? d.angle_a1 : (k == "angle_atom2") ? d.angle_a2 :
+         (k == "angle_atom3") ? d.angle_a3 : (k == "type") ? d.type_t : nullptr;
+}
+
+static void gather_subset_impl(Engine *e, const char *fn, const char *name, int type, int count, int ndata, const int *ids,
+                               void *data) {
+  const std::string k = name;
+  const bool dbl3 = type == 1 && count == 3 && (k == "x" || k == "v" || k == "f");
+  const bool img = type == 0 && k == "image" && (count == 1 || count == 3);
+  const bool host_only = type == 0 && count == 1 && (k == "id" || k == "mask" || k == "molecule");   // static per atom
+  const bool tagtab = type == 0 && ((k == "type" && count == 1) || (topo_width(e, k) == count && count > 0));
+  if (!dbl3 && !img && !host_only && !tagtab) throw LammpsError(std::string(fn) + ": unknown property name " + k);
+  check_ids(e, fn, ndata, ids);
+  const int K = ndata;
+  if (K == 0) return;
+  if (host_only || !device_is_newer(e)) {
+    double *od = (double *)data;
+    int *oi = (int *)data;
+    const int n = e->natoms;
+    for (int r = 0; r < K; r++) {
+      const int i = ids[r] - 1;
+      if (dbl3) {
+        const std::vector<double> &src = (k == "x") ? e->x : (k == "v") ? e->v : e->f;
+        for (int c = 0; c < 3; c++) od[3 * (size_t)r + c] = src[3 * (size_t)i + c];
+      } else if (k == "id") oi[r] = i + 1;
+      else if (k == "mask") oi[r] = (int)e->gmask.size() == n ? (e->gmask[i] | 1) : 1;
+      else if (k == "molecule") oi[r] = e->molecule[i];
+      else if (k == "type") oi[r] = e->type[i];
+      else if (img && count == 3) for (int c = 0; c < 3; c++) oi[3 * (size_t)r + c] = e->image[3 * (size_t)i + c];
+      else if (img) oi[r] = lammps_encode_image_flags(e->image[3 * i], e->image[3 * i + 1], e->image[3 * i + 2]);
+      else {
+        const std::vector<int> &src = *host_topo(e, k);
+        for (int c = 0; c < count; c++) oi[(size_t)r * count + c] = src[(size_t)i * count + c];
+      }
     }
+    return;
+  }
+  DeviceState &d = *e->dev;
+  const int prop = dbl3 ? (k == "x" ? SUBSET_X : SUBSET_V3) : img ? (count == 3 ? SUBSET_IMG3 : SUBSET_IMG1) : SUBSET_TAGTAB;
+  const size_t rowb = (size_t)count * (dbl3 ? sizeof(double) : sizeof(int));
+  std::vector<int> found(K);
+  std::vector<char> rows((size_t)K * rowb);
+  subset_gather(d, prop, k == "f" ? 1 : 0, tagtab ? dev_topo(d, k) : nullptr, count, K, ids, rows.data(), found.data());
+  if (d.dd && prop != SUBSET_TAGTAB) {
+    // every rank packed the rows it owns: one K-row all-gather completes them (found column included)
+    const int W = e->world;
+    const size_t per = (size_t)K * rowb + (size_t)K * sizeof(int);
+    std::vector<char> mine(per), all(per * W);
+    memcpy(mine.data(), rows.data(), (size_t)K * rowb);
+    memcpy(mine.data() + (size_t)K * rowb, found.data(), (size_t)K * sizeof(int));
+    e->comm->allgather_host(mine.data(), all.data(), per);
+    e->subset_comm_bytes += (double)per;
+    for (int r = 0; r < K; r++) {
+      int owner = -1;
+      for (int q = 0; q < W && owner < 0; q++) {
+        int fl;
+        memcpy(&fl, all.data() + per * q + (size_t)K * rowb + (size_t)r * sizeof(int), sizeof(int));
+        if (fl) owner = q;
+      }
+      if (owner < 0) throw LammpsError(std::string(fn) + ": atom ID " + std::to_string(ids[r]) + " is owned by no rank");
+      memcpy((char *)data + (size_t)r * rowb, all.data() + per * owner + (size_t)r * rowb, rowb);
+    }
+    return;
+  }
+  for (int r = 0; r < K; r++)
+    if (!found[r]) throw LammpsError(std::string(fn) + ": atom ID " + std::to_string(ids[r]) + " has no slot on the device");
+  memcpy(data, rows.data(), (size_t)K * rowb);
+}
+
+static bool fixes_on_groups(Engine *e) {
+  for (auto &f : e->fixes) if (f->groupbit != 1) return true;
+  return false;
+}
+
+static void scatter_subset_impl(Engine *e, const char *fn, const char *name, int type, int count, int ndata, const int *ids,
+                                void *data) {
+  const std::string k = name;
+  const bool dbl3 = type == 1 && count == 3 && (k == "x" || k == "v" || k == "f");
+  const bool img = type == 0 && k == "image" && (count == 1 || count == 3);
+  const bool typ = type == 0 && count == 1 && k == "type";
+  if (!dbl3 && !img && !typ) throw LammpsError(std::string(fn) + ": unknown property name " + k);
+  check_ids(e, fn, ndata, ids);
+  // a repeated ID takes its last row, as the reference's sequential loop leaves it
+  const size_t rowb = (size_t)count * (dbl3 ? sizeof(double) : sizeof(int));
+  std::vector<int> uid;
+  std::vector<char> urows;
+  {
+    std::vector<char> seen((size_t)e->natoms + 1, 0);
+    for (int r = ndata - 1; r >= 0; r--) {
+      if (seen[ids[r]]) continue;
+      seen[ids[r]] = 1;
+      uid.push_back(ids[r]);
+      urows.insert(urows.end(), (const char *)data + (size_t)r * rowb, (const char *)data + (size_t)(r + 1) * rowb);
+    }
+  }
+  const int K = (int)uid.size();
+  if (K == 0) return;
+  auto apply_host = [&]() {
+    for (int r = 0; r < K; r++) {
+      const int i = uid[r] - 1;
+      const char *src = urows.data() + (size_t)r * rowb;
+      if (dbl3) {
+        std::vector<double> &dst = (k == "x") ? e->x : (k == "v") ? e->v : e->f;
+        memcpy(&dst[3 * (size_t)i], src, rowb);
+      } else if (typ) memcpy(&e->type[i], src, sizeof(int));
+      else if (count == 3) memcpy(&e->image[3 * (size_t)i], src, rowb);
+      else { int im; memcpy(&im, src, sizeof(int)); lammps_decode_image_flags(im, &e->image[3 * (size_t)i]); }
+    }
+  };
+  if (!(e->dev && e->dev_current && e->dev->pos)) { apply_host(); return; }   // the host copies are the state
+  DeviceState &d = *e->dev;
+  // what cannot stay on the device takes the whole-system path (download, edit, re-upload at the next run):
+  //  - a new type for a bead while some fix acts on a group (its members' draws and masks travel with an upload);
+  //  - decomposed runs: moved beads that land beyond a neighbouring slab, or more of them than k_dd_leave can migrate
+  bool fallback = typ && fixes_on_groups(e);
+  if (d.dd && k == "x") {
+    std::vector<int> found(K);
+    std::vector<double> cur(3 * (size_t)K);
+    subset_gather(d, SUBSET_X, 0, nullptr, 3, K, uid.data(), cur.data(), found.data());
+    const int W = e->world, me = e->rank;
+    long leave = 0, far = 0;
+    for (int r = 0; r < K; r++) {
+      if (!found[r]) continue;
+      double z;
+      memcpy(&z, urows.data() + (size_t)r * rowb + 2 * sizeof(double), sizeof(double));
+      if (z < e->box.lo[2]) z += e->box.prd[2];          // the owner expression of Engine::upload / k_dd_classify
+      if (z >= e->box.hi[2]) z -= e->box.prd[2];
+      int owner = (int)((z - e->box.lo[2]) / (e->box.prd[2] / W));
+      owner = std::min(std::max(owner, 0), W - 1);
+      if (owner == me) continue;
+      leave++;
+      if (owner != (me + 1) % W && owner != (me + W - 1) % W) far++;
+    }
+    const long migcap = (long)d.npad / 4;                  // kernels_dd.hip dd_reneighbor: slots per direction
+    fallback = e->comm->allreduce_host_max((far > 0 || leave > migcap / 2) ? 1L : 0L) != 0;
+    e->subset_comm_bytes += (double)sizeof(long);
+  }
+  if (fallback) {
+    e->download();
+    apply_host();
+    e->dev_current = false;    // next run re-uploads
+    return;
+  }
+  const int prop = dbl3 ? (k == "x" ? SUBSET_X : SUBSET_V3) : typ ? SUBSET_TYPE : (count == 3 ? SUBSET_IMG3 : SUBSET_IMG1);
+  subset_scatter(d, prop, k == "f" ? 1 : 0, count, K, uid.data(), urows.data());
+  if (k == "x") d.bins_ready = false;      // bins a step kernel left behind belong to the old positions
+  if (e->host_current) apply_host();       // keep a current host copy current
+}
+
+// local order of the engine's one-rank reference (crank): order[r] = tag - 1 of the atom with local index r
+static std::vector<int> local_order(Engine *e) {
+  const int n = e->natoms;
+  std::vector<int> cr(e->crank.begin(), e->crank.begin() + n);
+  if (e->crank_on_device && e->dev && e->dev->crank) {
+    std::vector<int> c((size_t)n + 2);
+    HIP_CHECK(hipMemcpy(c.data(), e->dev->crank, c.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) cr[i] = c[i + 1];
+  }
+  std::vector<int> order(n, -1);
+  for (int i = 0; i < n; i++) {
+    if (cr[i] < 0 || cr[i] >= n || order[cr[i]] >= 0) throw LammpsError("internal: local order is not a permutation");
+    order[cr[i]] = i;
+  }
+  return order;
+}
+
+// gather_atoms_concat / gather_concat (src/library.cpp:2076-2224, :2834-3075): every atom, in local order
+static void gather_concat_impl(Engine *e, const char *fn, const char *name, int type, int count, void *data) {
+  const int n = e->natoms;
+  const size_t rowb = (size_t)count * (type == 1 ? sizeof(double) : sizeof(int));
+  std::vector<char> bytag((size_t)n * rowb);
+  gather_atoms_impl(e, fn, name, type, count, bytag.data());
+  const std::vector<int> order = local_order(e);
+  for (int r = 0; r < n; r++) memcpy((char *)data + (size_t)r * rowb, bytag.data() + (size_t)order[r] * rowb, rowb);
+}
+
+// lammps_gather / lammps_scatter and their subset forms (src/library.cpp:2615-3509): per-atom properties only - fix,
+// compute and custom per-atom names (f_, c_, d_, i_) have nothing per-atom to return on this path
+static void no_custom(const char *fn, const char *name) {
+  const std::string k = name;
+  if (k.rfind("f_", 0) == 0 || k.rfind("c_", 0) == 0 || k.rfind("d_", 0) == 0 || k.rfind("i_", 0) == 0)
+    throw LammpsError(std::string(fn) + ": unknown property name " + k);
+}
+
+void lammps_gather_atoms_subset(void *handle, char *name, int type, int count, int ndata, int *ids, void *data) {
+  BEGIN_CAPTURE gather_subset_impl(e, "lammps_gather_atoms_subset", name, type, count, ndata, ids, data); END_CAPTURE
+}
+void lammps_scatter_atoms_subset(void *handle, char *name, int type, int count, int ndata, int *ids, void *data) {
+  BEGIN_CAPTURE scatter_subset_impl(e, "lammps_scatter_atoms_subset", name, type, count, ndata, ids, data); END_CAPTURE
+}
+void lammps_gather_atoms_concat(void *handle, char *name, int type, int count, void *data) {
+  BEGIN_CAPTURE gather_concat_impl(e, "lammps_gather_atoms_concat", name, type, count, data); END_CAPTURE
+}
+void lammps_gather(void *handle, char *name, int type, int count, void *data) {
+  BEGIN_CAPTURE no_custom("lammps_gather", name); gather_atoms_impl(e, "lammps_gather", name, type, count, data); END_CAPTURE
+}
+void lammps_scatter(void *handle, char *name, int type, int count, void *data) {
+  BEGIN_CAPTURE no_custom("lammps_scatter", name); scatter_atoms_impl(e, "lammps_scatter", name, type, count, data); END_CAPTURE
+}
+void lammps_gather_concat(void *handle, char *name, int type, int count, void *data) {
+  BEGIN_CAPTURE no_custom("lammps_gather_concat", name); gather_concat_impl(e, "lammps_gather_concat", name, type, count, data); END_CAPTURE
+}
+void lammps_gather_subset(void *handle, char *name, int type, int count, int ndata, int *ids, void *data) {
+  BEGIN_CAPTURE
+    no_custom("lammps_gather_subset", name);
+    gather_subset_impl(e, "lammps_gather_subset", name, type, count, ndata, ids, data);
+  END_CAPTURE
+}
+void lammps_scatter_subset(void *handle, char *name, int type, int count, int ndata, int *ids, void *data) {
+  BEGIN_CAPTURE
+    no_custom("lammps_scatter_subset", name);
+    scatter_subset_impl(e, "lammps_scatter_subset", name, type, count, ndata, ids, data);
   END_CAPTURE
 }
 
-void lammps_scatter_atoms(void *handle, char *name, int type, int count, void *data) {
+// ---- computes (src/library.cpp:1555-1640).  The thermo computes the reference creates with every instance
+// (thermo_temp, thermo_pe, thermo_press; src/output.cpp) take their values from the thermo evaluation of the current step -
+// the device reductions thermo runs - and compute property/local from the bond tables ----
+enum { LMP_STYLE_GLOBAL = 0, LMP_STYLE_ATOM = 1, LMP_STYLE_LOCAL = 2 };
+enum { LMP_TYPE_SCALAR = 0, LMP_TYPE_VECTOR = 1, LMP_TYPE_ARRAY = 2, LMP_SIZE_VECTOR = 3, LMP_SIZE_ROWS = 4, LMP_SIZE_COLS = 5 };
+
+// sum(m v_i v_j) over all atoms, order xx yy zz xy xz yz (compute temp's vector before the mvv2e factor)
+static void ke_tensor_now(Engine *e, double k6[6]) {
+  if (e->dev && e->dev_current && e->dev->pos) {      // the device holds the state (possibly the host as well)
+    TypeTables tt{};
+    for (int t = 1; t <= e->ntypes; t++) tt.mass[t] = e->mass[t];
+    ke_tensor(*e->dev, tt, k6);
+    if (e->world > 1) e->comm->allreduce_host_sum(k6, 6);
+    return;
+  }
+  for (int c = 0; c < 6; c++) k6[c] = 0.0;
+  for (int i = 0; i < e->natoms; i++) {
+    const double m = e->mass[e->type[i]], *v = &e->v[3 * (size_t)i];
+    k6[0] += m * v[0] * v[0]; k6[1] += m * v[1] * v[1]; k6[2] += m * v[2] * v[2];
+    k6[3] += m * v[0] * v[1]; k6[4] += m * v[0] * v[2]; k6[5] += m * v[1] * v[2];
+  }
+}
+
+void *lammps_extract_compute(void *handle, char *id, int style, int type) {
+  void *result = nullptr;
   BEGIN_CAPTURE
+    const std::string c = id;
+    const bool thermo_c = c == "thermo_temp" || c == "thermo_pe" || c == "thermo_press";
+    if (!thermo_c && !e->computes_local.count(c)) return nullptr;
+    Engine::ComputeCache &cc = e->compute_cache[c];
+    const bool fresh = cc.invoked == e->ntimestep && cc.stamp == e->thermo_log.size();
+    if (thermo_c) {
+      if (style != LMP_STYLE_GLOBAL) return nullptr;                         // no per-atom / local data
+      if (type == LMP_TYPE_ARRAY || type == LMP_SIZE_ROWS || type == LMP_SIZE_COLS) return nullptr;   // no array_flag
+      if (c == "thermo_pe" && type != LMP_TYPE_SCALAR) return nullptr;       // compute pe: scalar only
+      if (!fresh) {
+        // energies and the virial exist for a step whose forces were computed with energy: the thermo row of this step
+        const ThermoRow &r = e->last_thermo;
+        const bool tallied = !e->thermo_log.empty() && r.step == e->ntimestep;
+        const double dof = 3.0 * e->natoms - 3.0;
+        const double vol = e->box.prd[0] * e->box.prd[1] * e->box.prd[2];
+        double k6[6];
+        if (c == "thermo_pe") {
+          if (!tallied) throw LammpsError("Energy was not tallied on needed timestep");   // src/compute_pe.cpp
+          cc.scalar = r.evdwl + (r.ebond + r.eangle);                       // compute pe is not normalized by natoms
+        } else if (c == "thermo_temp") {
+          ke_tensor_now(e, k6);
+          cc.vector.assign(6, 0.0);
+          for (int q = 0; q < 6; q++) cc.vector[q] = k6[q] * e->mvv2e;       // src/compute_temp.cpp compute_vector
+          cc.scalar = tallied ? r.temp : (dof > 0 ? (k6[0] + k6[1] + k6[2]) * e->mvv2e / (dof * e->boltz) : 0.0);
+        } else {
+          if (!tallied) throw LammpsError("Virial was not tallied on needed timestep");   // src/compute_pressure.cpp
+          cc.scalar = r.press;
+          cc.vector.assign(6, 0.0);
+          if (r.has_ptensor) for (int q = 0; q < 6; q++) cc.vector[q] = r.ptensor[q];
+          else {
+            ke_tensor_now(e, k6);     // the expression of Engine::eval_thermo (src/compute_pressure.cpp:244-290)
+            for (int q = 0; q < 6; q++) cc.vector[q] = (k6[q] * e->mvv2e + r.virial[q]) / vol * e->nktv2p;
+          }
+        }
+        cc.size_vector = (int)cc.vector.size();
+        cc.invoked = e->ntimestep;
+        cc.stamp = e->thermo_log.size();
+      }
+      if (type == LMP_TYPE_SCALAR) result = &cc.scalar;
+      else if (type == LMP_TYPE_VECTOR) result = cc.vector.data();
+      else if (type == LMP_SIZE_VECTOR) result = &cc.size_vector;
+      return result;
+    }
+    // compute property/local (btype batom1 batom2): one row per bond, listed once from the lower ID, both atoms in the
+    // compute's group (src/compute_property_local.cpp:420-480; the rows dump local writes)
+    if (style != LMP_STYLE_LOCAL) return nullptr;
+    if (!fresh) {
+      e->download();
+      const std::vector<std::string> &attrs = e->computes_local[c];
+      const int bit = e->computes_local_bit.count(c) ? e->computes_local_bit[c] : 1;
+      auto member = [&](int i) { return bit == 1 || (!e->gmask.empty() && (e->gmask[i] & bit)); };
+      const int nc = (int)attrs.size();
+      cc.vector.clear();
+      for (int i = 0; i < e->natoms; i++)
+        for (int m = 0; m < e->num_bond[i]; m++) {
+          const int bt = e->bond_type[(size_t)i * e->bpa + m], j = e->bond_atom[(size_t)i * e->bpa + m];
+          if (bt == 0 || i + 1 > j || !member(i) || !member(j - 1)) continue;
+          for (auto &a : attrs) cc.vector.push_back(a == "btype" ? bt : a == "batom1" ? i + 1 : j);
+        }
+      cc.size_rows = nc ? (int)(cc.vector.size() / nc) : 0;
+      cc.size_cols = nc > 1 ? nc : 0;                  // one attribute: vector_local, size_local_cols = 0
+      cc.rows.resize(cc.size_rows);
+      for (int r = 0; r < cc.size_rows; r++) cc.rows[r] = cc.vector.data() + (size_t)r * nc;
+      cc.invoked = e->ntimestep;
+      cc.stamp = e->thermo_log.size();
+    }
+    if (type == LMP_TYPE_SCALAR || type == LMP_SIZE_ROWS) result = &cc.size_rows;
+    else if (type == LMP_SIZE_COLS) result = &cc.size_cols;
+    else if (type == LMP_TYPE_VECTOR && cc.size_cols == 0) result = cc.vector.data();
+    else if (type == LMP_TYPE_ARRAY && cc.size_cols > 0) result = cc.rows.data();
+  END_CAPTURE
+  return result;
+}
+
+// ---- variables (src/library.cpp:1859-1940) ----
+void *lammps_extract_variable(void *handle, char *name, char * /*group*/) {
+  void *result = nullptr;
+  BEGIN_CAPTURE
+    auto it = e->variables.find(name);
+    if (it == e->variables.end()) return nullptr;
+    auto vi = e->var_info.find(name);
+    if (vi != e->var_info.end() && vi->second.style == "equal") {
+      double *d = (double *)malloc(sizeof(double));       // released by the caller with lammps_free
+      *d = e->evaluate(it->second);
+      result = d;
+    } else result = (void *)it->second.c_str();           // index / loop / string (and -var): borrowed
+  END_CAPTURE
+  return result;
+}
+// the style of a variable as the later library.h's lammps_extract_variable_datatype reports it: LMP_VAR_EQUAL (0) or
+// LMP_VAR_STRING (3, index / loop / string), -1 if there is no such variable; tells a caller which pointer to expect
+int lammps_extract_variable_datatype(void *handle, const char *name) {
+  Engine *e = (Engine *)handle;
+  if (!e->variables.count(name)) return -1;
+  auto vi = e->var_info.find(name);
+  return (vi != e->var_info.end() && vi->second.style == "equal") ? 0 : 3;
+}
+int lammps_set_variable(void *handle, char *name, char *str) {
+  int err = -1;
+  BEGIN_CAPTURE
+    auto vi = e->var_info.find(name);                     // Variable::set_string: string style only
+    if (vi != e->var_info.end() && vi->second.style == "string") {
+      vi->second.values = {str};
+      e->variables[name] = str;
+      err = 0;
+    }
+  END_CAPTURE
+  return err;
+}
+
+// ---- introspection (src/library.cpp:973, :1407, :4241-4500) ----
+enum { LAMMPS_INT = 0, LAMMPS_INT_2D = 1, LAMMPS_DOUBLE = 2, LAMMPS_DOUBLE_2D = 3, LAMMPS_INT64 = 4, LAMMPS_STRING = 6 };
+int lammps_extract_global_datatype(void *, const char *name) {
+  const std::string k = name;
+  if (k == "dt" || k == "atime" || k == "boxlo" || k == "boxhi" || k == "boltz") return LAMMPS_DOUBLE;
+  if (k == "ntimestep" || k == "atimestep" || k == "natoms" || k == "nbonds") return LAMMPS_INT64;
+  if (k == "ntypes") return LAMMPS_INT;
+  if (k == "units") return LAMMPS_STRING;
+  return -1;
+}
+int lammps_extract_atom_datatype(void *, const char *name) {
+  const std::string k = name;
+  if (k == "x" || k == "v" || k == "f") return LAMMPS_DOUBLE_2D;
+  if (k == "mass") return LAMMPS_DOUBLE;
+  if (k == "type" || k == "id" || k == "mask" || k == "image" || k == "molecule") return LAMMPS_INT;
+  return -1;
+}
+
+// styles: the ones lammps_has_style knows, in this order
+static const std::vector<std::pair<std::string, std::vector<std::string>>> &style_table() {
+  static const std::vector<std::pair<std::string, std::vector<std::string>>> t = {
+      {"atom", {"angle", "atomic", "bond", "full", "molecular"}},
+      {"bond", {"fene", "harmonic", "hybrid", "none", "zero"}},
+      {"compute", {"property/local"}},
+      {"dump", {"atom", "custom", "dcd", "local"}},
+      {"fix", {"bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve"}},
+      {"pair", {"lj/cut", "none", "zero"}},
+  };
+  return t;
+}
+static const std::vector<std::string> *styles_of(const char *category) {
+  for (auto &c : style_table()) if (c.first == category) return &c.second;
+  return nullptr;
+}
+int lammps_style_count(void *, const char *category) {
+  const std::vector<std::string> *s = styles_of(category);
+  return s ? (int)s->size() : 0;
+}
+int lammps_style_name(void *, const char *category, int idx, char *buffer, int buf_size) {
+  const std::vector<std::string> *s = styles_of(category);
+  if (!s || idx < 0 || idx >= (int)s->size()) { if (buf_size > 0) buffer[0] = '\0'; return 0; }
+  snprintf(buffer, buf_size, "%s", (*s)[idx].c_str());
+  return 1;
+}
+
+// IDs by category (src/library.cpp:4348-4500): compute, dump, fix, group, molecule, region, variable
+static std::vector<std::string> ids_of(Engine *e, const std::string &c) {
+  std::vector<std::string> out;
+  if (c == "compute") {
+    out = {"thermo_temp", "thermo_press", "thermo_pe"};        // created with every instance (src/output.cpp:60-80)
+    for (auto &kv : e->computes_local) out.push_back(kv.first);
+  } else if (c == "dump") for (auto &d : e->dumps) out.push_back(d.id);
+  else if (c == "fix") for (auto &f : e->fixes) out.push_back(f->id);
+  else if (c == "group") { for (auto &g : e->group_names) if (!g.empty()) out.push_back(g); }
+  else if (c == "region") for (auto &kv : e->regions) out.push_back(kv.first);
+  else if (c == "variable") for (auto &kv : e->variables) out.push_back(kv.first);
+  return out;                                                   // molecule: this path has no molecule templates
+}
+int lammps_has_id(void *handle, const char *category, const char *name) {
+  for (auto &s : ids_of((Engine *)handle, category)) if (s == name) return 1;
+  return 0;
+}
+int lammps_id_count(void *handle, const char *category) { return (int)ids_of((Engine *)handle, category).size(); }
+int lammps_id_name(void *handle, const char *category, int idx, char *buffer, int buf_size) {
+  const std::vector<std::string> ids = ids_of((Engine *)handle, category);
+  if (idx < 0 || idx >= (int)ids.size()) { if (buf_size > 0) buffer[0] = '\0'; return 0; }
+  snprintf(buffer, buf_size, "%s", ids[idx].c_str());
+  return 1;
+}
+
+// the packages of the reference build this engine stands for (SURVEY: MOLECULE, MC, MISC, USER-LE)
+int lammps_config_package_name(int idx, char *buffer, int buf_size) {
+  static const char *pkgs[] = {"MC", "MISC", "MOLECULE", "USER-LE"};
+  if (idx < 0 || idx >= 4) { if (buf_size > 0) buffer[0] = '\0'; return 0; }
+  snprintf(buffer, buf_size, "%s", pkgs[idx]);
+  return 1;
+}
+// src/library.cpp:4063-4072 (Info::get_os_info + get_compiler_info): operating system, then the compiler
+void lammps_get_os_info(char *buffer, int buf_size) {
+  if (buf_size <= 0) return;
+  struct utsname u;
+  std::string txt = "unknown";
+  if (uname(&u) == 0) txt = std::string(u.sysname) + " \"" + u.release + "\" " + u.version + " " + u.machine;
+  txt += "\n";
+#if defined(__clang_version__)
+  txt += std::string("Clang C++ ") + __clang_version__;
+#else
+  txt += "C++";
+#endif
+  txt += " with OpenMP not enabled\n";
+  snprintf(buffer, buf_size, "%s", txt.c_str());
+}
+int lammps_get_mpi_comm(void *) { return -1; }   // no MPI on this path (src/library.cpp:780-790 without MPI)
+
+// src/library.cpp:691-720: a new orthogonal box; the device copies are re-uploaded at the next run
+void lammps_reset_box(void *handle, double *boxlo, double *boxhi, double /*xy*/, double /*yz*/, double /*xz*/) {
+  BEGIN_CAPTURE
+    if (!e->box_exist) { e->warning("Calling lammps_reset_box without a box"); return; }
     e->download();
-    std::string k = name;
-    int n = e->natoms;
-    if (type == 1 && count == 3 && (k == "x" || k == "v" || k == "f")) {
-      std::vector<double> &dst = (k == "x") ? e->x : (k == "v") ? e->v : e->f;
-      memcpy(dst.data(), data, 3 * (size_t)n * sizeof(double));
-    } else if (type == 0 && count == 1 && k == "type") memcpy(e->type.data(), data, n * sizeof(int));
-    else if (type == 0 && count == 3 && k == "image") memcpy(e->image.data(), data, 3 * (size_t)n * sizeof(int));
-    else throw LammpsError("lammps_scatter_atoms: unknown property name " + k);
-    e->dev_current = false;   // next run re-uploads
+    for (int k = 0; k < 3; k++) {
+      e->box.lo[k] = boxlo[k]; e->box.hi[k] = boxhi[k];
+      e->box.prd[k] = e->box.hi[k] - e->box.lo[k];
+      e->box.half[k] = 0.5 * e->box.prd[k];
+      e->box.iprd[k] = 1.0 / e->box.prd[k];
+    }
+    e->dev_current = false;
   END_CAPTURE
 }
+
+// Timer::force_timeout (src/timer.h): the current run ends at the next step boundary, later runs do nothing.  A caller of
+// this single-threaded engine is never inside a run when it calls this, so it is the next run that ends (at once)
+void lammps_force_timeout(void *handle) { ((Engine *)handle)->timeout_forced = true; }
+
+// ---- out of scope, exported with an explicit error (no fake data) ----
+// neighbor lists (src/library.cpp:3869-4060): one GPU has no ghost atoms and the lists are stored by cell slot, so the
+// reference's list indices have no meaning here
+static void no_neighlist(Engine *e) {
+  e->last_error = "neighbor list access is not supported";
+  e->has_error = true;
+}
+int lammps_find_pair_neighlist(void *handle, char *, int, int, int) { no_neighlist((Engine *)handle); return -1; }
+int lammps_find_fix_neighlist(void *handle, char *, int) { no_neighlist((Engine *)handle); return -1; }
+int lammps_find_compute_neighlist(void *handle, char *, int) { no_neighlist((Engine *)handle); return -1; }
+int lammps_neighlist_num_elements(void *handle, int) { no_neighlist((Engine *)handle); return 0; }
+void lammps_neighlist_element_neighbors(void *handle, int, int, int *iatom, int *numneigh, int **neighbors) {
+  no_neighlist((Engine *)handle);
+  if (iatom) *iatom = -1;
+  if (numneigh) *numneigh = 0;
+  if (neighbors) *neighbors = nullptr;
+}
+// fix external (src/library.cpp:4578-4650): there is no such fix style here, so no fix ID is ever one of it
+static void no_fix_external(Engine *e, const char *id) {
+  const std::string msg = e->find_fix(id ? id : "") ? std::string("Fix '") + id + "' is not of style external!"
+                                                    : std::string("Can not find fix with ID '") + (id ? id : "") + "'!";
+  e->last_error = msg;
+  e->has_error = true;
+}
+void lammps_set_fix_external_callback(void *handle, char *id, void *, void *) { no_fix_external((Engine *)handle, id); }
+void lammps_fix_external_set_energy_global(void *handle, char *id, double) { no_fix_external((Engine *)handle, id); }
+void lammps_fix_external_set_virial_global(void *handle, char *id, double *) { no_fix_external((Engine *)handle, id); }
+
+// src/library.cpp:163-200: the MPI_Comm argument of an MPI-less (STUBS) build is an int and means nothing here
+void *lammps_open(int argc, char **argv, int /*comm*/, void **ptr) { return lammps_open_no_mpi(argc, argv, ptr); }
 
 int lammps_version(void *) { return 20201029; }
 /* src/library.cpp lammps_encode_image_flags: 10 bits per dimension, offset 512 (LAMMPS_SMALLBIG) */
@@ -239,13 +762,8 @@ int lammps_get_last_error_message(void *handle, char *buffer, int buf_size) {
 }
 int lammps_config_has_exceptions(void) { return 1; }
 int lammps_has_style(void *, const char *category, const char *name) {
-  std::string c = category, s = name;
-  if (c == "fix") return s == "nve" || s == "langevin" || s == "extrusion" || s == "ex_load" || s == "ex_unload" || s == "bond/break" || s == "bond/create";
-  if (c == "pair") return s == "lj/cut" || s == "zero" || s == "none";
-  if (c == "dump") return s == "atom" || s == "custom" || s == "local" || s == "dcd";
-  if (c == "compute") return s == "property/local";
-  if (c == "bond") return s == "fene" || s == "harmonic" || s == "hybrid" || s == "zero" || s == "none";
-  if (c == "atom") return s == "bond" || s == "molecular" || s == "atomic" || s == "full" || s == "angle";
+  const std::vector<std::string> *s = styles_of(category);
+  if (s) for (auto &x : *s) if (x == name) return 1;
   return 0;
 }
 
@@ -302,6 +820,8 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "nlocal") return e->dev ? (double)e->dev->n : 0.0;
   if (k == "nghost") return e->dev ? (double)e->dev->nghost : 0.0;
   if (k == "fene_warnings") return e->dev && e->dev->flags_h ? (double)e->dev->flags_h[FLAG_FENE_WARN] : 0.0;
+  if (k == "host_downloads") return (double)e->host_downloads;          // whole-system downloads (Engine::download)
+  if (k == "subset_comm_bytes") return e->subset_comm_bytes;           // this rank's share of the subset calls' collectives
   return -1.0;
 }
 

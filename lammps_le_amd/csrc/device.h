@@ -239,6 +239,9 @@ struct DeviceState {
   // ---- kernel timing (HIP events on the launch stream) ----
   std::vector<hipEvent_t> ev0, ev1;
   size_t ev_used = 0;
+  // ---- C-ABI subset calls (kernels_capi.hip): staging block of the K requested rows ----
+  void *capi_buf = nullptr;
+  size_t capi_cap = 0;
 };
 
 // ------------------------------- launchers (kernels_*.hip) -------------------------------------
@@ -354,5 +357,15 @@ void dd_alloc(DeviceState &d, int world);
 // bits and O(extruders) position records instead of an all-gather of every bead's (tag, x, xhold) (kernels_dd.hip
 // dd_gather_needed, kernels_le.hip launch_ex_load).  Other visit orders keep the whole-system gather.
 inline bool dd_le_fast(const DeviceState &d) { return d.dd && d.ident_order && !d.newton_pair && !getenv("LAMMPS_LE_DD_FULL_GATHER"); }
+
+// ID-addressed rows for the C-ABI subset calls (kernels_capi.hip).  ids: K tags in 1..natoms (host memory).
+// SUBSET_X: x (double, 3); SUBSET_V3: v (which 0) or f (which 1) (double, 3); SUBSET_IMG3 / SUBSET_IMG1: image flags unpacked /
+// packed (int, 3 / 1); SUBSET_TAGTAB: row t of the tag-indexed int table `tab` of width `count` (gather only); SUBSET_TYPE:
+// type (scatter only).  Gather: `found[i]` = 1 where this rank holds row i (always, for a tag table); rows it does not hold
+// are left unwritten.  Scatter writes the rows this rank owns.  Both synchronise the stream.
+enum SubsetProp { SUBSET_X = 0, SUBSET_V3 = 1, SUBSET_IMG3 = 2, SUBSET_IMG1 = 3, SUBSET_TAGTAB = 4, SUBSET_TYPE = 5 };
+void subset_gather(DeviceState &d, int prop, int which, const int *tab, int count, int K, const int *ids, void *out_rows,
+                   int *found);
+void subset_scatter(DeviceState &d, int prop, int which, int count, int K, const int *ids, const void *rows);
 
 }  // namespace lmp_le

@@ -346,6 +346,7 @@ void Engine::upload() {
 void Engine::download() {
   if (!dev || !dev_current || host_current) return;
   DeviceState &d = *dev;
+  host_downloads++;
   if (d.dd) {
     // collective: every rank ends up with the whole system (rows: tag x y z type vx vy vz fx fy fz ix iy iz)
     std::vector<double> rows;
@@ -1196,6 +1197,7 @@ void Engine::print_timing_breakdown(long nsteps) {
 
 void Engine::run(long nsteps) {
   if (nsteps < 0) throw LammpsError("Invalid run command N value");
+  if (timeout_forced) return;       // src/run.cpp:47: after Timer::force_timeout a run does nothing
   // checks every rank fails identically are made before anything collective starts: they must not cost the communicator
   for (int a = 1; a <= nangletypes && apa > 0 && nangles > 0 && !angle_style_name.empty() && angle_style_name != "none" && angle_style_name != "zero"; a++)
     if (!angtab.style[a]) throw LammpsError("All angle coeffs are not set");

@@ -382,6 +382,9 @@ class Engine {
   void device_init();                 // throws LammpsError if no HIP device
   void upload();                      // host -> device (after read_data / scatter)
   void download();                    // device -> host (x, v, f, type, image, topology)
+  long host_downloads = 0;            // whole-system downloads so far (lammps_le_stat "host_downloads")
+  double subset_comm_bytes = 0.0;     // bytes this rank contributed to the collectives of the C-ABI subset calls
+  bool timeout_forced = false;        // lammps_force_timeout: runs end at once, as after Timer::force_timeout
   void reneighbor(bool defer_check = false, bool sort_now = false);   // pbc + spatial sort + cell lists + neighbor list + bond table
   bool reneigh_pending = false;       // the build's overflow / error flags are published but not yet looked at
   bool finish_reneighbor();           // waits for them; false = a list overflowed (nothing may depend on the lists yet)
@@ -416,6 +419,17 @@ class Engine {
   std::map<std::string, std::vector<int>> scratch_i;
   std::vector<double *> scratch_rows;
   double scratch_scalar = 0.0;
+  int scratch_int = 0;
+  // lammps_extract_compute: values of the thermo computes and the step they were evaluated on (Compute::invoked_*)
+  struct ComputeCache {
+    long invoked = -1;                 // ntimestep of the evaluation ...
+    size_t stamp = 0;                  // ... and thermo_log.size() then (a run in between re-evaluates)
+    double scalar = 0.0;
+    std::vector<double> vector;        // global vector, or property/local values (rows x cols)
+    std::vector<double *> rows;        // property/local with several attributes: row pointers (array_local)
+    int size_vector = 0, size_rows = 0, size_cols = 0;
+  };
+  std::map<std::string, ComputeCache> compute_cache;
 };
 
 // helpers
