@@ -835,6 +835,64 @@ extern "C" void lammps_le_test_ranmars(int seed, long long skip, int n, double *
   for (int i = 0; i < n; i++) out[i] = r.uniform();
 }
 
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): the neighbor list of the last build,
+// decoded on the host and named by TAGS.  Pair entries (i, j, special level bits of the word) go to itag / jtag / code,
+// at most `cap` of them; the bond entries that open every list go to btag / bjtag / btype, at most `bcap` of them (their
+// number to *nbond); owned_tag[nlocal] and xbuild[3 * nlocal] receive the owned beads in list order and the positions the
+// list was built from (xhold).  Rank-local: a decomposed run hands out the lists of the beads this rank owns, ghost
+// neighbors by their tag.  Returns the number of pair entries there are (a first call with cap = 0 sizes the buffers),
+// -1 with the error string set when no list has been built yet.  Output pointers may be null.
+extern "C" long long lammps_le_test_neighbor_list(void *handle, long long cap, int *itag, int *jtag, int *code,
+                                                  int *btag, int *bjtag, int *btype, long long bcap, long long *nbond,
+                                                  int *owned_tag, double *xbuild) {
+  long long npair = -1;
+  BEGIN_CAPTURE
+  if (!e->dev || !e->dev->neigh || !e->dev->numneigh || e->reneigh_pending)
+    throw LammpsError("lammps_le_test_neighbor_list: no neighbor list has been built yet");
+  DeviceState &d = *e->dev;
+  stream_sync(d);
+  const size_t n = (size_t)d.n, nslots = n + (size_t)(d.dd ? d.nghost : 0), np = (size_t)d.npad;
+  std::vector<int> nn(n), tg(nslots), row(n);
+  std::vector<double4> xh(n);
+  HIP_CHECK(hipMemcpy(nn.data(), d.numneigh, n * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(tg.data(), d.tag, nslots * sizeof(int), hipMemcpyDeviceToHost));
+  HIP_CHECK(hipMemcpy(xh.data(), d.xhold, n * sizeof(double4), hipMemcpyDeviceToHost));
+  int longest = 0;
+  for (size_t s = 0; s < n; s++) longest = std::max(longest, nn[s] & NN_COUNT_MASK);
+  if (longest > d.maxneigh) throw LammpsError("lammps_le_test_neighbor_list: a count word exceeds the table");
+  std::vector<int> tab((size_t)longest * np);      // the table is column-major: row k of every bead is contiguous
+  if (longest) HIP_CHECK(hipMemcpy(tab.data(), d.neigh, tab.size() * sizeof(int), hipMemcpyDeviceToHost));
+  auto tag_of = [&](int q) -> int {
+    if (q < 0 || (size_t)q >= nslots) throw LammpsError("lammps_le_test_neighbor_list: entry points outside the bead slots");
+    return tg[(size_t)q];
+  };
+  long long np_out = 0, nb_out = 0;
+  for (size_t s = 0; s < n; s++) {
+    if (owned_tag) owned_tag[s] = tg[s];
+    if (xbuild) { xbuild[3 * s] = xh[s].x; xbuild[3 * s + 1] = xh[s].y; xbuild[3 * s + 2] = xh[s].z; }
+    const int cnt = nn[s] & NN_COUNT_MASK, nb = (nn[s] >> NN_BOND_SHIFT) & NN_NBOND_MASK;
+    if (nb > cnt) throw LammpsError("lammps_le_test_neighbor_list: more bond entries than entries");
+    for (int k = 0; k < cnt; k++) {
+      const int w = tab[(size_t)k * np + s];
+      if (k < nb) {
+        if (nb_out < bcap && btag && bjtag && btype) {
+          btag[nb_out] = tg[s]; bjtag[nb_out] = tag_of(w & BOND_IDX_MASK); btype[nb_out] = (w >> BOND_TYPE_SHIFT) & 0x1F;
+        }
+        nb_out++;
+      } else {
+        if (np_out < cap && itag && jtag && code) {
+          itag[np_out] = tg[s]; jtag[np_out] = tag_of(w & NEIGH_MASK); code[np_out] = (w >> NEIGH_SB_SHIFT) & 3;
+        }
+        np_out++;
+      }
+    }
+  }
+  if (nbond) *nbond = nb_out;
+  npair = np_out;
+  END_CAPTURE
+  return npair;
+}
+
 // ---- ranks: one process per GPU (bench.py passes the ncclUniqueId it broadcast with torch.distributed) ----
 extern "C" int lammps_le_comm_unique_id(char *out128) {
   try { lmp_le::comm_unique_id(out128); return 0; } catch (const std::exception &ex) { fprintf(stderr, "%s\n", ex.what()); return 1; }

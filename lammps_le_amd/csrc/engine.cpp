@@ -473,6 +473,8 @@ static void check_device_error(Engine *e, DeviceState &d) {
 // the check (~25 us) is hidden behind that kernel instead of idling the GPU once per rebuild.
 void Engine::reneighbor(bool defer_check, bool sort_now) {
   DeviceState &d = *dev;
+  // (`pair_style zero` builds the pair list like any pair style - that is what the style is for, src/pair_zero.cpp - although
+  //  no force kernel reads its pair entries: without a pair force they take the bonds from the bond-partner table)
   // (read at every rebuild, not cached: the test that sets it shares its process with tests that must not see it)
   const char *ovf = getenv("LAMMPS_LE_TEST_OVERFLOW_AT");
   const long test_overflow_at = ovf ? atol(ovf) : -1;
@@ -481,10 +483,10 @@ void Engine::reneighbor(bool defer_check, bool sort_now) {
   // pbc + ownership + cell order, then - on a sort step - the reference's Atom::sort (src/verlet.cpp:270-286: after pbc,
   // BEFORE neighbor->build: the pair list of this very build is stored in the new local order, which decides whose special
   // list a pair's status comes from when the lists are asymmetric), then the lists
-  if (d.dd) dd_reneighbor(d, *comm, cutneighmax * cutneighmax, special_lj, pair_lj, false);
+  if (d.dd) dd_reneighbor(d, *comm, cutneighmax * cutneighmax, special_lj, pair_lj || pair_zero, false);
   else launch_sort_owned(d);
   if (sort_now) emulate_atom_sort();
-  launch_lists(d, cutneighmax * cutneighmax, special_lj, pair_lj);
+  launch_lists(d, cutneighmax * cutneighmax, special_lj, pair_lj || pair_zero);
   // (decomposed: the border pass of the rebuild has also checked that this rank's Langevin pools hold the draws of the beads
   //  it owns now - FLAG_RNG_MISS, kernels_dd.hip k_dd_borders)
   if (defer_check && !d.dd) {
@@ -533,7 +535,7 @@ void Engine::regrow_lists() {
     dev_alloc_neigh(d, d.flags_h[FLAG_MAXNEIGH] + 16);
     HIP_CHECK(hipMemsetAsync(d.flags + FLAG_NEIGH_OVERFLOW, 0, sizeof(int), d.stream));
     HIP_CHECK(hipMemsetAsync(d.flags + FLAG_MAXNEIGH, 0, sizeof(int), d.stream));
-    launch_lists(d, cutneighmax * cutneighmax, special_lj, pair_lj);
+    launch_lists(d, cutneighmax * cutneighmax, special_lj, pair_lj || pair_zero);
     sync_flags(d);
     check_device_error(this, d);
   }

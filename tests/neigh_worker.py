@@ -1,0 +1,69 @@
+"""The engine's neighbor list through the test hook lammps_le_test_neighbor_list; also one rank of a run in a process of its
+own (test helper, launched by test_gpu_neigh.py: decomposed runs, and runs under an environment variable that the engine
+latches when it allocates).
+usage: neigh_worker.py RANK WORLD SESSION SYSTEM.pkl SCRIPT.txt OUT.npz   ->  OUT.npz.rRANK.npz"""
+import ctypes as C
+import os
+import pickle
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+
+
+def fetch_list(lmp):
+    """dict(itag, jtag, code: pair entries in list order; btag, bjtag, btype: bond entries; owned: tags of the owned beads in
+    list order; xbuild[nlocal, 3]: the positions the list was built from)."""
+    fn = lmp.lib.lammps_le_test_neighbor_list
+    ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    fn.restype = C.c_longlong
+    fn.argtypes = [C.c_void_p, C.c_longlong, ip, ip, ip, ip, ip, ip, C.c_longlong, C.POINTER(C.c_longlong), ip, dp]
+    nbond = C.c_longlong(-1)
+    npair = fn(lmp.lmp, 0, None, None, None, None, None, None, 0, C.byref(nbond), None, None)
+    lmp._check()
+    assert npair >= 0 and nbond.value >= 0
+    nlocal = int(lmp.stat("nlocal"))
+    iarr = lambda m: np.full(max(int(m), 1), -7, dtype=np.int32)
+    out = dict(itag=iarr(npair), jtag=iarr(npair), code=iarr(npair), btag=iarr(nbond.value), bjtag=iarr(nbond.value),
+               btype=iarr(nbond.value), owned=iarr(nlocal), xbuild=np.full((max(nlocal, 1), 3), np.nan))
+    p = lambda a: a.ctypes.data_as(ip)
+    nbond2 = C.c_longlong(-1)
+    again = fn(lmp.lmp, npair, p(out["itag"]), p(out["jtag"]), p(out["code"]), p(out["btag"]), p(out["bjtag"]), p(out["btype"]),
+               nbond.value, C.byref(nbond2), p(out["owned"]), out["xbuild"].ctypes.data_as(dp))
+    lmp._check()
+    assert again == npair and nbond2.value == nbond.value
+    for k in ("itag", "jtag", "code"):
+        out[k] = out[k][:npair]
+    for k in ("btag", "bjtag", "btype"):
+        out[k] = out[k][:nbond.value]
+    out["owned"], out["xbuild"] = out["owned"][:nlocal], out["xbuild"][:nlocal]
+    return out
+
+
+def main():
+    from lammps_le_amd import lammps
+    from systems import write_data
+    rank, world, session, sysfile, scriptfile, out = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6]
+    system = pickle.load(open(sysfile, "rb"))
+    lmp = lammps(cmdargs=["-screen", "none"])
+    if world > 1:
+        lmp.comm_init("shm", rank, world, session=session)
+    for ln in open(scriptfile).read().split("\n"):
+        w = ln.split("#")[0].split()
+        if w and w[0] == "read_data":
+            path = os.path.join(os.path.dirname(out), "data.r%d" % rank)
+            write_data(path, system)
+            ln = "read_data " + path
+        lmp.command(ln)
+    res = fetch_list(lmp)
+    # (gathers and the pair count are collective: every rank calls them)
+    res.update(x=lmp.gather("x"), image=lmp.gather("image"), num_bond=lmp.gather("num_bond"), bond_type=lmp.gather("bond_type"), bond_atom=lmp.gather("bond_atom"),
+               neigh_pairs=np.array([lmp.stat("neigh_pairs")]), builds=np.array([lmp.stat("neigh_builds")]),
+               maxneigh=np.array([lmp.stat("maxneigh")]))
+    np.savez("%s.r%d.npz" % (out, rank), **res)
+    lmp.close()
+
+
+if __name__ == "__main__":
+    main()
