@@ -129,7 +129,9 @@ int  lammps_has_style(void *handle, const char *category, const char *name);
  * then asks which end stores each pair); with ranks: "comm_nranks", "comm_bytes_allgather", "comm_bytes_allreduce",
  * "halo_window_exchanges", "halo_window_mismatches", "halo_fused", "rng_segments", "rng_segments_held",
  * "rng_late_generations"; "host_downloads" (whole-system device -> host copies so far), "subset_comm_bytes" (bytes this rank
- * contributed to the collectives of the subset calls).  An unknown name returns -1. */
+ * contributed to the collectives of the subset calls); "steps_fused" / "steps_fused_thermo" / "steps_unfused" (time steps of
+ * the last run by the path they took: the fused step kernel, its energy variant on a thermo step, the unfused kernels) and
+ * "steps_fused_group" (those of "steps_fused" that took the group variant).  An unknown name returns -1. */
 double lammps_le_stat(void *handle, const char *name);
 /* the thermo lines printed so far as numbers: rows of 7 doubles (step, temp, epair, emol, etotal, press, bonds); returns the
  * number of rows, writes at most max_rows (the reference's counterpart is parsing its log file) */

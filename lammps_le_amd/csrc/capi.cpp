@@ -784,6 +784,12 @@ double lammps_le_stat(void *handle, const char *name) {
   std::string k = name;
   if (k == "loop_time") return e->loop_time;
   if (k == "neigh_builds") return (double)e->neigh_builds;
+  // time steps of the last run by the path they took: the step kernel (steps_fused_group of them its group variant), its
+  // energy variant on a thermo step, the unfused kernels; the three add up to the steps of the run
+  if (k == "steps_fused") return (double)e->steps_fused;
+  if (k == "steps_fused_group") return (double)e->steps_fused_group;
+  if (k == "steps_fused_thermo") return (double)e->steps_fused_thermo;
+  if (k == "steps_unfused") return (double)e->steps_unfused;
   if (k == "neigh_time" || k == "time_neigh") return e->timers[Engine::T_NEIGH];
   if (k == "time_pair") return e->timers[Engine::T_PAIR];
   if (k == "time_bond") return e->timers[Engine::T_BOND];

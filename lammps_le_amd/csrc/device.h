@@ -10,6 +10,8 @@
 #include <cstdint>
 #include <vector>
 
+#include <type_traits>
+
 #include "engine.h"
 
 namespace lmp_le {
@@ -244,6 +246,15 @@ struct DeviceState {
   size_t capi_cap = 0;
 };
 
+// with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...): where the launchers turn run-time
+// flags into template arguments.  f is a generic lambda; `if constexpr` inside it keeps combinations that do not exist
+// from being instantiated.
+template <class F> inline void with_flags(F &&f) { f(); }
+template <class F, class... Rest> inline void with_flags(F &&f, bool b, Rest... rest) {
+  if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 // ------------------------------- launchers (kernels_*.hip) -------------------------------------
 void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxspecial, const Box &box,
                double cutneigh);
@@ -254,12 +265,17 @@ void dev_alloc_neigh(DeviceState &d, int maxneigh);
 void launch_initial_integrate(DeviceState &d, const TypeTables &tt, double dtv, double triggersq, bool check, int groupbit = 1);
 void launch_force(DeviceState &d, const BondTable &bt, const double special_lj[4], bool eflag, bool has_pair, int parts = 3);
 void launch_flevel_copy(DeviceState &d, double *flevel, bool to_level, bool add);
-void launch_step(DeviceState &d, const BondTable &bt, const double special_lj[4], const TypeTables &tt, bool langevin,
-                 bool next, bool ident, bool has_pair, double dtv, double triggersq, bool check, hipEvent_t ev_start = nullptr,
-                 hipEvent_t ev_stop = nullptr, int which = -1, bool swap_buffers = true, bool angle_forces = false,
-                 bool eflag = false, int nvebit = 1, int lgbit = 1);    // group bits != 1: fix nve / fix langevin on a group (GRP variant)
-bool step_fuses_groups(const DeviceState &d, bool has_pair, bool angles);   // fix nve / fix langevin on groups inside the step kernel
-bool step_fuses_energy(const DeviceState &d, bool has_pair);   // a thermo step can be one launch of the step kernel's energy variant
+// the fused step kernel: the variant `plan` names (step_plan.h), fused force + Langevin + final_integrate [+ the next
+// initial_integrate]; what a launch needs beyond the plan and the device state:
+struct StepArgs {
+  const BondTable *bt = nullptr;
+  const double *special_lj = nullptr;
+  const TypeTables *tt = nullptr;
+  double dtv = 0.0, triggersq = 0.0;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // sampled launches: the kernel's own begin / end timestamps
+  bool swap_buffers = true;                           // a `next` launch leaves the new positions in d.pos
+};
+void launch_step(DeviceState &d, const StepPlan &plan, const StepArgs &args);
 void launch_langevin(DeviceState &d, const TypeTables &tt, bool identity_rank, bool fuse_final, int groupbit = 1);
 // `zero yes`: after launch_langevin and before the draws are released - the members' mean random force off every member
 void launch_langevin_zero(DeviceState &d, const TypeTables &tt, bool identity_rank, int groupbit, long members,
@@ -273,7 +289,6 @@ void ke_tensor(DeviceState &d, const TypeTables &tt, double *out6);
 void launch_angle(DeviceState &d, const AngleTable &at, bool eflag, bool overwrite = false);
 void launch_angle_list(DeviceState &d);       // at every reneighbor of a run with an angle style
 void upload_angle_table(DeviceState &d, const AngleTable &at);   // before the first fused step of a run with an angle style
-bool step_fuses_angles(const DeviceState &d, bool has_pair);
 void reduce_angle_partials(DeviceState &d, double *out8);
 // reductions: returns sums of `partial` columns on the host (synchronises the stream)
 void reduce_partials(DeviceState &d, double *out16);

@@ -875,6 +875,7 @@ void Engine::setup() {
   reneighbor(false, sortfreq > 0);    // pbc + (spatial sort) + Atom::sort + lists; ncalls reset below
   double s1 = wall();
   neigh_builds = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
@@ -898,29 +899,24 @@ void Engine::iterate(long nsteps) {
   FixLangevin *lg = the_langevin(this);
   int nnve = count_nve(this);
   double triggersq = 0.25 * skin * skin;
-  bool fusable = (nnve == 1) && !getenv("LAMMPS_LE_NO_FUSE");
-  // fix nve / fix langevin on a group other than all: the group variant of the fused step kernel (one fix nve, a pair style;
-  // thermo steps and everything else take the unfused kernels, which test the bead's group bits)
+  step_knobs = StepKnobs();
+  // What the engine itself knows to rule the fused step kernel out; whether the kernel covers the step, and with which of
+  // its variants, is plan_step's answer (step_plan.h).  fix nve / fix langevin on a group other than all: the group variant
+  // of the step kernel; thermo steps and everything else take the unfused kernels, which test the bead's group bits
   const std::vector<int> nbits = nve_bits(this);
-  const bool grouped = md_fixes_on_groups(this);
-  int gnve = 1, glg = 1;
-  if (grouped) {
-    if (nnve == 1 && step_fuses_groups(d, pair_lj, angles_active()) && !(lg && langevin_members == 0)) {
-      gnve = nbits[0];
-      glg = lg ? lg->groupbit : 1;
-    }
-    else fusable = false;
-  }
+  bool fusable = nnve == 1;
+  if (md_fixes_on_groups(this) && lg && langevin_members == 0) fusable = false;
   if (lg && lg->zeroflag) fusable = false;         // (`zero yes` needs the group's summed random force before final_integrate)
   // bond morse (the reference's unit-test partner of bond hybrid, not a style of the chromatin model) lives in the
   // unfused force kernel only: its exp() would cost the fused step kernel registers every run pays for
   for (int b = 1; b <= nbondtypes; b++) if (bondtab.style[b] == 3) fusable = false;
-  // angles (semiflexible chains): a kernel of their own writes the angle forces right before the fused step
-  // kernel, which adds them to its sums (decomposed runs too: every rank for the beads it owns)
+  // angles (semiflexible chains): a whole step evaluates the listed angles inside the step kernel (decomposed
+  // runs too: every rank for the beads it owns)
   const bool ang = angles_active();
-  if (ang && !step_fuses_angles(d, pair_lj)) fusable = false;      // (no pair style: force kernel -> angle kernel -> integrate kernels)
   if (ang && fusable) upload_angle_table(d, angtab);
-  bool ident = d.ident_order;
+  StepRequest rq;
+  rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_lj; rq.angles = ang;
+  rq.nvebit = fusable ? nbits[0] : 1; rq.lgbit = lg ? lg->groupbit : 1;
   bool pre_integrated = false;
   // halo/compute overlap issues the per-step halo on a second stream.  With RCCL that means two streams feeding ONE
   // communicator (ordered by events, but never run on multi-GPU hardware): kept to the test transports unless
@@ -942,6 +938,12 @@ void Engine::iterate(long nsteps) {
     const bool restart_now = restart_every > 0 && ntimestep % restart_every == 0;
     const bool dump_now = (!dumps.empty() && dump_due(ntimestep)) || restart_now;   // needs the complete state of this step: unfused path
     TypeTables tt = make_tables(this, lg);
+    // the plan of this step: a dump / restart needs the complete state of the step, which the unfused kernels leave
+    rq.next = it + 1 < nsteps; rq.thermo = eflag; rq.which = -1; rq.check = false;
+    auto plan_now = [&]() { return fusable && !dump_now ? plan_step(d.n, d.dd != 0, rq, step_knobs) : StepPlan(); };
+    StepPlan plan = plan_now();
+    StepArgs sa;
+    sa.bt = &bondtab; sa.special_lj = special_lj; sa.tt = &tt; sa.dtv = dt; sa.triggersq = triggersq;
     stamp();
     if (!pre_integrated) {
       bool will_check = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
@@ -952,7 +954,7 @@ void Engine::iterate(long nsteps) {
     if (decide()) {
       const bool sort_due = sortfreq > 0 && ntimestep >= nextsort;
       stamp();
-      reneighbor(fusable && !eflag && !dump_now && !sort_due, sort_due);
+      reneighbor(plan.fused && !plan.ef && !sort_due, sort_due);     // (a whole fused step follows: the check waits behind it)
       stamp(T_NEIGH);
     } else {
       stamp();
@@ -960,9 +962,12 @@ void Engine::iterate(long nsteps) {
       stamp(T_COMM);
     }
     stamp();
-    if (fusable && !eflag && !dump_now) {
-      bool next = (it + 1 < nsteps);
-      bool check_next = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
+    // (the rebuild may have moved beads between the ranks, and the displacement test counts from it)
+    rq.check = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
+    rq.cells = d.cell_count && d.ncells > 0;
+    plan = plan_now();
+    if (plan.fused && !plan.ef) {
+      const bool next = rq.next;
       if (lg) langevin_draws(this, lg);
       bool timed = timed_begin(this);
       // opt-in (LAMMPS_LE_OVERLAP=1): parity-tested on one GPU with the in-process and mailbox transports, but the
@@ -972,11 +977,13 @@ void Engine::iterate(long nsteps) {
       if (d.dd && next && overlap) {
         // phase 1 = beads that are sent to a neighbour or read a ghost; their new positions start travelling on
         // comm_stream (ghost slots of the NEXT step) while phase 0 - the interior - is still being computed
-        launch_step(d, bondtab, special_lj, tt, lg != nullptr, next, ident, pair_lj, dt, triggersq, check_next, nullptr,
-                    nullptr, 1, false, false, false, gnve, glg);
+        sa.swap_buffers = false;
+        rq.which = 1;
+        launch_step(d, plan_now(), sa);
         HIP_CHECK(hipEventRecord(d.ev_phase1, d.stream));
-        launch_step(d, bondtab, special_lj, tt, lg != nullptr, next, ident, pair_lj, dt, triggersq, check_next,
-                    timed ? d.ev0[d.ev_used] : nullptr, timed ? d.ev1[d.ev_used] : nullptr, 0, false, false, false, gnve, glg);
+        rq.which = 0;
+        if (timed) { sa.ev_start = d.ev0[d.ev_used]; sa.ev_stop = d.ev1[d.ev_used]; }
+        launch_step(d, plan_now(), sa);
         HIP_CHECK(hipStreamWaitEvent(d.comm_stream, d.ev_phase1, 0));
         dd_halo(d, *comm, d.comm_stream, d.pos_tmp, d.pos_tmp);
         HIP_CHECK(hipEventRecord(d.ev_halo, d.comm_stream));
@@ -986,33 +993,34 @@ void Engine::iterate(long nsteps) {
       } else {
         // (a whole step evaluates the listed angles inside the step kernel; the last step of a run, which stores forces,
         //  takes them from the angle kernel)
-        if (ang && !next) launch_angle(d, angtab, false, true);
-        launch_step(d, bondtab, special_lj, tt, lg != nullptr, next, ident, pair_lj, dt, triggersq, check_next,
-                    timed ? d.ev0[d.ev_used] : nullptr, timed ? d.ev1[d.ev_used] : nullptr, -1, true, ang, false, gnve, glg);
+        if (timed) { sa.ev_start = d.ev0[d.ev_used]; sa.ev_stop = d.ev1[d.ev_used]; }
+        if (plan.ang && !next) launch_angle(d, angtab, false, true);
+        launch_step(d, plan, sa);
         if (!finish_reneighbor()) {
           // a list of the build that preceded this launch overflowed: the kernel saw the flag and stored nothing.
           // Undo the launch on the host side, grow the table, rebuild, launch again.
           if (next) std::swap(d.pos, d.pos_tmp);
           regrow_lists();
-          if (ang && !next) launch_angle(d, angtab, false, true);
-          launch_step(d, bondtab, special_lj, tt, lg != nullptr, next, ident, pair_lj, dt, triggersq, check_next,
-                      timed ? d.ev0[d.ev_used] : nullptr, timed ? d.ev1[d.ev_used] : nullptr, -1, true, ang, false, gnve, glg);
+          if (plan.ang && !next) launch_angle(d, angtab, false, true);
+          launch_step(d, plan, sa);
         }
       }
       if (timed) d.ev_used++;
       if (lg) rng_langevin_consumed(d);
       pre_integrated = next;
+      steps_fused++;
+      if (plan.grp) steps_fused_group++;
       stamp(T_PAIR);          // the fused kernel: pair + bond + post_force + final_integrate (+ next initial_integrate)
-    } else if (fusable && eflag && !dump_now && !ang && !grouped && step_fuses_energy(d, pair_lj)) {
+    } else if (plan.fused) {
       // a thermo step without dumps: the step kernel's energy variant - forces, energies, virial, post_force and
       // final_integrate in one pass; the next step starts with its own initial_integrate (thermo reads the velocities
       // of the END of this step)
       if (!finish_reneighbor()) regrow_lists();
       if (lg) langevin_draws(this, lg);
-      launch_step(d, bondtab, special_lj, tt, lg != nullptr, false, ident, pair_lj, dt, triggersq, false, nullptr, nullptr, -1,
-                  true, false, true);
+      launch_step(d, plan, sa);
       if (lg) rng_langevin_consumed(d);
       pre_integrated = false;
+      steps_fused_thermo++;
       stamp(T_PAIR);
       last_thermo = eval_thermo(true);
       thermo_log.push_back(last_thermo);
@@ -1022,6 +1030,7 @@ void Engine::iterate(long nsteps) {
       if (!finish_reneighbor()) regrow_lists();
       if (d.dd) dd_halo_wait(d);
       compute_forces(eflag);
+      steps_unfused++;
       stamp(T_PAIR);          // k_force: pair + bond in one pass
       // (Langevin and the final half-kick in one kernel only when both fixes act on the same atoms)
       const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag;
@@ -1073,6 +1082,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   respa_flevel_n = need;
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
   for (int l = 0; l <= top; l++) {
     respa_level_forces(l);
     launch_flevel_copy(d, respa_flevel[l], true, false);
@@ -1142,6 +1152,7 @@ void Engine::respa_iterate(long nsteps) {                                    // 
   DeviceState &d = *dev;
   for (long it = 0; it < nsteps; it++) {
     ntimestep++;
+    steps_unfused++;
     const bool eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0);
     const bool restart_now = restart_every > 0 && ntimestep % restart_every == 0;
     const bool dump_now = (!dumps.empty() && dump_due(ntimestep)) || restart_now;

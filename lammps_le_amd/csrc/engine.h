@@ -13,6 +13,8 @@
 #include <string>
 #include <vector>
 
+#include "step_plan.h"
+
 namespace lmp_le {
 
 struct LammpsError : std::runtime_error {
@@ -295,6 +297,10 @@ class Engine {
   std::vector<ThermoRow> thermo_log;
   double loop_time = 0.0;
   long neigh_builds = 0, neigh_dangerous = 0;
+  // time steps of the current run by the path they took (lammps_le_stat): the step kernel (of which: its group variant), the
+  // step kernel's energy variant on a thermo step, the unfused kernels
+  long steps_fused = 0, steps_fused_group = 0, steps_fused_thermo = 0, steps_unfused = 0;
+  StepKnobs step_knobs;        // the step kernel's environment switches as they stood when the current run began
   long rng_late_count = 0;     // decomposed runs: late generations of skipped Langevin stream segments (lammps_le_stat)
   int ago = 0;
   // Timer sections of the loop (src/timer.h:25-28); wall clock between stamps as src/timer.cpp:100-135.  The GPU runs

@@ -26,8 +26,6 @@ constexpr int BLOCK = 256;
 #ifndef STEP_WAVES_PER_SIMD
 #define STEP_WAVES_PER_SIMD 4
 #endif
-constexpr int AHEAD_MAX_BEADS = 64000;   // k_step: partner / first-stage loads issued ahead of their use up to this size
-constexpr int LPB4_MAX_BEADS = 50000;   // k_step: four lanes per bead up to this many (owned) beads, see k_step
 #define TWO_1_3 1.2599210498948732
 
 // XCD-aware block remap (cdna_hip_programming.md T1): blocks b and b+8 share an XCD, so give
@@ -818,12 +816,10 @@ void launch_langevin_zero(DeviceState &d, const TypeTables &tt, bool ident, int 
   const int *gm = groupbit != 1 ? d.gmask : (const int *)nullptr;
   const int *rk = groupbit != 1 ? d.lgrank : d.crank;
   if (groupbit != 1) ident = false;
-  if (ident)
-    hipLaunchKernelGGL((k_langevin_fsum<true>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, rk, d.rng_out, tt, gm,
+  with_flags([&](auto I) {
+    hipLaunchKernelGGL((k_langevin_fsum<I>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, rk, d.rng_out, tt, gm,
                        groupbit, d.lgsum);
-  else
-    hipLaunchKernelGGL((k_langevin_fsum<false>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, rk, d.rng_out, tt, gm,
-                       groupbit, d.lgsum);
+  }, ident);
   hipLaunchKernelGGL(k_langevin_fsum_total, dim3(1), dim3(BLOCK), 0, d.stream, nb, host_sum3 ? 1.0 : 1.0 / (double)members, d.lgsum);
   if (host_sum3) {
     HIP_CHECK(hipMemcpyAsync(d.partial_h, d.lgsum + (size_t)nb * 16, 3 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
@@ -848,12 +844,10 @@ void launch_langevin(DeviceState &d, const TypeTables &tt, bool ident, bool fuse
   const int *gm = groupbit != 1 ? d.gmask : (const int *)nullptr;
   const int *rk = groupbit != 1 ? d.lgrank : d.crank;       // rank among the members of the group
   if (groupbit != 1) ident = false;
-#define LGV(F, I)                                                                                               \
-  hipLaunchKernelGGL((k_langevin<F, I>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, rk,       \
-                     d.rng_out, d.v[0], d.v[1], d.v[2], d.f[0], d.f[1], d.f[2], tt, gm, groupbit)
-  if (fuse_final) { if (ident) LGV(true, true); else LGV(true, false); }
-  else { if (ident) LGV(false, true); else LGV(false, false); }
-#undef LGV
+  with_flags([&](auto F, auto I) {
+    hipLaunchKernelGGL((k_langevin<F, I>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, rk,
+                       d.rng_out, d.v[0], d.v[1], d.v[2], d.f[0], d.f[1], d.f[2], tt, gm, groupbit);
+  }, fuse_final, ident);
 }
 // run_style respa: FixRespa's per-level force arrays (src/fix_respa.cpp), kept by tag so that the cell sort of a rebuild
 // does not have to carry them; to_level: flevel[tag[p]] = f[p], else f[p] = flevel[tag[p]] (+= when `add`)
@@ -932,57 +926,70 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
   ForceArgs A = force_args(d, sl);
   int grid = xcd_grid(A.nblocks);
   if (!has_pair) parts &= 2;
-  if (parts != 3) {
-    if (parts == 0) {
-      for (int k = 0; k < 3; k++) HIP_CHECK(hipMemsetAsync(d.f[k], 0, (size_t)d.n * sizeof(double), d.stream));
-    } else if (parts == 2) {      // bonds only: straight from the bond-partner table
-      if (eflag) hipLaunchKernelGGL((k_force<true, false>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
-      else hipLaunchKernelGGL((k_force<false, false>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
-    } else {                      // pairs only
-      A.diag = 1;
-      if (eflag) hipLaunchKernelGGL((k_force<true, true, true>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
-      else hipLaunchKernelGGL((k_force<false, true, true>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
-    }
+  if (parts == 0) {
+    for (int k = 0; k < 3; k++) HIP_CHECK(hipMemsetAsync(d.f[k], 0, (size_t)d.n * sizeof(double), d.stream));
     return;
   }
-#define FRC(E, P)                                                                                            \
-  hipLaunchKernelGGL((k_force<E, P>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1],   \
-                     d.f[2], d.partial, d.flags)
-  if (eflag) { if (has_pair) FRC(true, true); else FRC(true, false); }
-  else { if (has_pair) FRC(false, true); else FRC(false, false); }
-#undef FRC
+  if (parts == 1) A.diag = 1;      // pairs only (bonds only: straight from the bond-partner table)
+  with_flags([&](auto E, auto P, auto NOBOND) {
+    if constexpr (P || !NOBOND)
+      hipLaunchKernelGGL((k_force<E, P, NOBOND>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
+  }, eflag, (parts & 1) != 0, parts == 1);
 }
-// which shape of the step kernel a system of this size takes (environment overrides for experiments)
-static bool step_lpb4(const DeviceState &d) {
-  static const int lpb_env = getenv("LAMMPS_LE_LPB") ? atoi(getenv("LAMMPS_LE_LPB")) : 0;
-  static const int lpb_max_n = getenv("LAMMPS_LE_LPB_MAX_N") ? atoi(getenv("LAMMPS_LE_LPB_MAX_N")) : LPB4_MAX_BEADS;
-  return lpb_env ? lpb_env == 4 : d.n <= lpb_max_n;
+// The instantiations of k_step that exist (what step_plan.h plans with; implies the two static_asserts inside k_step):
+constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP) {
+  if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
+  if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
+  if (EF) return !N && P && LPB == 1 && !AHEAD && !ANG;      // thermo step in one pass: L, I = 4
+  if (ANG) return P && LPB == 1;                             // angles inside the step: L, N, I, AHEAD = 16
+  return LPB == 1 || AHEAD;                                  // L, N, I, P x {four lanes, one lane ahead, one lane} = 48
 }
-static bool step_ahead(const DeviceState &d) {
-  static const int ahead_max_n = getenv("LAMMPS_LE_AHEAD_MAX_N") ? atoi(getenv("LAMMPS_LE_AHEAD_MAX_N")) : AHEAD_MAX_BEADS;
-  return d.n <= ahead_max_n;
+constexpr int count_step_variants() {
+  int c = 0;
+  for (int m = 0; m < 1024; m++)
+    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512);
+  return c;
 }
-// a thermo step as ONE pass (k_step<.., EF>): one GPU, a pair style, the throughput shape of the kernel (one lane per bead)
-bool step_fuses_energy(const DeviceState &d, bool has_pair) {
-  static const bool off = getenv("LAMMPS_LE_NO_FUSED_THERMO") != nullptr;
-  return has_pair && !d.dd && !step_lpb4(d) && !step_ahead(d) && !off;
+static_assert(count_step_variants() == 77, "the set of k_step instantiations changed");
+// f(k_step<the plan's ten template arguments>); false: there is no such instantiation
+template <class F>
+static bool with_step_kernel(const StepPlan &p, F &&f) {
+  bool found = false;
+  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R) {
+    constexpr int W = W4 ? 4 : 1;
+    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R)) { f(k_step<L, N, I, P, W, D, H, G, E, R>); found = true; }
+  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp);
+  return found;
 }
-// fix nve / fix langevin on groups inside the step kernel (GRP instantiations): a pair style; with an angle style only the
-// throughput shape (the look-ahead shape of small systems has no group + angle instantiation)
-bool step_fuses_groups(const DeviceState &d, bool has_pair, bool angles) {
-  static const bool off = getenv("LAMMPS_LE_NO_FUSED_GROUPS") != nullptr;
-  return has_pair && !off && !(angles && step_ahead(d));
+// ev_start / ev_stop (sampled launches only) take the kernel's own begin / end timestamps from its dispatch packet,
+// the same clock rocprofv3 --kernel-trace reports
+static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArgs &A, const StepArgs &a, hipEvent_t ev_start,
+                               hipEvent_t ev_stop) {
+  // a whole step of a run with an angle style (NEXT) evaluates the listed angles inside the kernel: records, counts and the
+  // coefficient table travel in the three force pointers, which a NEXT launch does not otherwise use (step_body)
+  double *pf0 = d.f[0], *pf1 = d.f[1], *pf2 = d.f[2];
+  if (p.ang && p.next) {
+    if (!d.eff_rec || !d.eff_n || !d.angtab_dev) throw LammpsError("internal: fused angle step without angle records");
+    pf0 = reinterpret_cast<double *>(d.eff_rec); pf1 = reinterpret_cast<double *>(d.eff_n); pf2 = reinterpret_cast<double *>(d.angtab_dev);
+  }
+  if (p.grp && !d.gmask) throw LammpsError("internal: fused step on groups without group masks");
+  // a thermo step (EF): block totals of energies and virial through the pos_next argument, which it does not use otherwise.
+  // Fixes on groups (GRP): the draws of a thermostat on a group go by the rank among its members
+  double4 *pos_next = p.ef ? reinterpret_cast<double4 *>(d.partial) : d.pos_tmp;
+  const int *ranks = p.member_ranks ? d.lgrank : d.crank, *gmask = p.grp ? d.gmask : nullptr;
+  const int grid = xcd_grid(A.nblocks);
+  const bool found = p.fused && with_step_kernel(p, [&](auto kernel) {
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, d.tag, ranks,
+                          d.rng_out, d.v[0], d.v[1], d.v[2], pf0, pf1, pf2, pos_next, d.xhold, a.dtv, a.triggersq, p.check ? 1 : 0,
+                          d.flags, d.phase, p.which, gmask, p.nvebit, p.lgbit);
+  });
+  if (!found) throw LammpsError("internal: the step plan names a variant of the step kernel that does not exist");
 }
-// fused force + Langevin + final_integrate [+ next initial_integrate]; swaps the position buffers when `next`
-void launch_step(DeviceState &d, const BondTable &bt, const double sl[4], const TypeTables &tt, bool langevin,
-                 bool next, bool ident, bool has_pair, double dtv, double triggersq, bool check, hipEvent_t ev_start,
-                 hipEvent_t ev_stop, int which, bool swap_buffers, bool angle_forces, bool eflag, int nvebit, int lgbit) {
-  ForceArgs A = force_args(d, sl);
-  const bool grp = nvebit != 1 || lgbit != 1;        // fix nve / fix langevin on a group: the GRP instantiations
-  if (grp && (eflag || !has_pair || !d.gmask)) throw LammpsError("internal: group variant of the fused step asked for a launch it does not cover");
-  if (d.dd && next && d.sendslot && !d.sendslot_fallback) {
+void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
+  ForceArgs A = force_args(d, a.special_lj);
+  if (d.dd && p.next && d.sendslot && !d.sendslot_fallback) {
     A.sendslot = d.sendslot;
-    if (d.fast_halo && d.direct_recv && which < 0) {
+    if (d.fast_halo && d.direct_recv && p.which < 0) {
       // the neighbours' windows, in their sorted ghost order: what I send down arrives there "from above" and vice versa
       const int parity = (int)((d.halo_seq + 1u) & 1u);
       A.send_dn = d.peer_win[0] + (size_t)(parity * 2 + 1) * d.halo_cap;
@@ -995,95 +1002,41 @@ void launch_step(DeviceState &d, const BondTable &bt, const double sl[4], const 
       d.packed_peer = 0;
     }
   }
-  // lanes per bead: 4 while the launch is latency-bound (few wavefronts per SIMD), 1 once it is throughput-bound
-  const bool lpb4 = step_lpb4(d) && !angle_forces && !grp;     // (angle / group runs: one lane per bead, see step_fuses_angles)
-  if (grp && angle_forces && step_ahead(d)) throw LammpsError("internal: group variant with angles covers the throughput shape only");
-  if (angle_forces && !has_pair) throw LammpsError("internal: fused angle step without a pair style");
-  const bool ahead = step_ahead(d) && !grp;
-  if (eflag && (next || angle_forces || which >= 0 || !step_fuses_energy(d, has_pair)))
-    throw LammpsError("internal: energy variant of the fused step asked for a launch it does not cover");
-  // diagnostics only (LAMMPS_LE_STEP_LDS_PAD=bytes): unused dynamic LDS per workgroup, to lower the occupancy on purpose
-  static const unsigned lds_pad = getenv("LAMMPS_LE_STEP_LDS_PAD") ? (unsigned)atoi(getenv("LAMMPS_LE_STEP_LDS_PAD")) : 0u;
-  if (lpb4) { A.nblocks = (d.n + BLOCK / 4 - 1) / (BLOCK / 4); A.maxrow = (d.maxneigh - 4) / 4; }
-  // positions binned by this launch: single GPU, whole-step launch with a displacement test in it, one lane per bead (with
-  // four lanes per bead - small systems - it was measured slower than the separate k_wrap_bin: 62.2k vs 64.5k steps/s at 32k)
-  static const bool no_fused_bin = getenv("LAMMPS_LE_NO_FUSED_BIN") != nullptr;
-  const bool bin = check && next && !d.dd && which < 0 && !lpb4 && !no_fused_bin && d.cell_count && d.ncells > 0;
-  if (bin) {
+  if (p.lpb == 4) { A.nblocks = (d.n + BLOCK / 4 - 1) / (BLOCK / 4); A.maxrow = (d.maxneigh - 4) / 4; }
+  if (p.bin) {
     // the counts are zero unless an earlier launch binned and no rebuild consumed them (the scan zeroes what it reads)
     if (d.cell_count_dirty) HIP_CHECK(hipMemsetAsync(d.cell_count, 0, (size_t)(d.ncells + 1) * sizeof(int), d.stream));
     d.cell_count_dirty = true;
     A.bin = 1;
   }
-  d.bins_ready = bin;
-  int grid = xcd_grid(A.nblocks);
-  // ev_start / ev_stop (sampled launches only) take the kernel's own begin / end timestamps from its dispatch packet,
-  // the same clock rocprofv3 --kernel-trace reports
-  // a whole step of a run with an angle style (NEXT) evaluates the listed angles inside the kernel: records, counts and the
-  // coefficient table travel in the three force pointers, which a NEXT launch does not otherwise use (step_body)
-  double *pf0 = d.f[0], *pf1 = d.f[1], *pf2 = d.f[2];
-  if (angle_forces && next) {
-    if (!d.eff_rec || !d.eff_n || !d.angtab_dev) throw LammpsError("internal: fused angle step without angle records");
-    pf0 = reinterpret_cast<double *>(d.eff_rec); pf1 = reinterpret_cast<double *>(d.eff_n); pf2 = reinterpret_cast<double *>(d.angtab_dev);
-  }
-#define STPL(L, N, I, P, W, D, H) STPA(L, N, I, P, W, D, H, false)
-#define STPA(L, N, I, P, W, D, H, G)                                                                         \
-  hipExtLaunchKernelGGL((k_step<L, N, I, P, W, D, H, G>), dim3(grid), dim3(BLOCK), lds_pad, d.stream, ev_start, ev_stop, 0, A, bt, \
-                        d.box, tt, d.tag, d.crank, d.rng_out, d.v[0], d.v[1], d.v[2], pf0, pf1, pf2,    \
-                        d.pos_tmp, d.xhold, dtv, triggersq, check ? 1 : 0, d.flags, d.phase, which, (const int *)nullptr, 1, 1)
-#define STP(L, N, I, P) do { if (angle_forces) { if (ahead) STPA(L, N, I, true, 1, false, true, true); else STPA(L, N, I, true, 1, false, false, true); } \
-    else if (lpb4) STPL(L, N, I, P, 4, false, true); else if (ahead) STPL(L, N, I, P, 1, false, true); else STPL(L, N, I, P, 1, false, false); } while (0)
-  int key = (langevin ? 8 : 0) | (next ? 4 : 0) | (ident ? 2 : 0) | (has_pair ? 1 : 0);
-  if (eflag) {      // thermo step: energies and virial in the same pass (block totals through the unused pos_next argument)
-#define STPE(L, I)                                                                                              \
-  hipExtLaunchKernelGGL((k_step<L, false, I, true, 1, false, false, false, true>), dim3(grid), dim3(BLOCK), lds_pad, d.stream, ev_start, \
-                        ev_stop, 0, A, bt, d.box, tt, d.tag, d.crank, d.rng_out, d.v[0], d.v[1], d.v[2], d.f[0], d.f[1], d.f[2],  \
-                        reinterpret_cast<double4 *>(d.partial), d.xhold, dtv, triggersq, 0, d.flags, d.phase, which, (const int *)nullptr, 1, 1)
-    if (langevin) { if (ident) STPE(true, true); else STPE(true, false); }
-    else { if (ident) STPE(false, true); else STPE(false, false); }
-#undef STPE
-    return;
-  }
+  d.bins_ready = p.bin;
   // LAMMPS_LE_DIAG_STEP=bits: the same kernel is launched once more BEFORE the real launch with parts switched off
   // (1 bonds, 2 pair loop, 4 draws, 8 pair gathers replaced by coalesced loads, 128 nothing); it writes only the second position buffer, which the real launch
   // overwrites, so the run is physically unchanged and a kernel trace shows what each part costs
-  static const int diag_step = getenv("LAMMPS_LE_DIAG_STEP") ? atoi(getenv("LAMMPS_LE_DIAG_STEP")) : 0;
-  if (diag_step && key == 15 && which < 0 && !lpb4) {
+  if (p.diag_bits) {
+    StepPlan q;
+    q.fused = q.langevin = q.next = q.ident = q.pair = q.diag = true;
+    q.check = p.check; q.which = p.which; q.lds_pad = p.lds_pad;
     ForceArgs R = A;
-    A.diag = diag_step | 64; A.bin = 0;
-    hipEvent_t e0 = ev_start, e1 = ev_stop;
-    ev_start = ev_stop = nullptr;
-    STPL(true, true, true, true, 1, true, false);
-    A = R; ev_start = e0; ev_stop = e1;
+    R.diag = p.diag_bits | 64; R.bin = 0;
+    launch_step_kernel(d, q, R, a, nullptr, nullptr);
   }
-  if (grp) {      // one lane per bead, ranks from a table: the draws of a thermostat on a group go by the rank among its members
-    const int *ranks = d.lg_grouped ? d.lgrank : d.crank;
-#define STPG(L, N, G)                                                                                           \
-  hipExtLaunchKernelGGL((k_step<L, N, false, true, 1, false, false, G, false, true>), dim3(grid), dim3(BLOCK), lds_pad, d.stream, \
-                        ev_start, ev_stop, 0, A, bt, d.box, tt, d.tag, ranks, d.rng_out, d.v[0], d.v[1], d.v[2], pf0, pf1, \
-                        pf2, d.pos_tmp, d.xhold, dtv, triggersq, check ? 1 : 0, d.flags, d.phase, which, d.gmask, nvebit, lgbit)
-#define STPGA(L, N) do { if (angle_forces) STPG(L, N, true); else STPG(L, N, false); } while (0)
-    if (langevin) { if (next) STPGA(true, true); else STPGA(true, false); }
-    else { if (next) STPGA(false, true); else STPGA(false, false); }
-#undef STPGA
-#undef STPG
-    if (next && swap_buffers) std::swap(d.pos, d.pos_tmp);
-    return;
-  }
-  switch (key) {
-    case 0: STP(false, false, false, false); break;  case 1: STP(false, false, false, true); break;
-    case 2: STP(false, false, true, false); break;   case 3: STP(false, false, true, true); break;
-    case 4: STP(false, true, false, false); break;   case 5: STP(false, true, false, true); break;
-    case 6: STP(false, true, true, false); break;    case 7: STP(false, true, true, true); break;
-    case 8: STP(true, false, false, false); break;   case 9: STP(true, false, false, true); break;
-    case 10: STP(true, false, true, false); break;   case 11: STP(true, false, true, true); break;
-    case 12: STP(true, true, false, false); break;   case 13: STP(true, true, false, true); break;
-    case 14: STP(true, true, true, false); break;    case 15: STP(true, true, true, true); break;
-  }
-#undef STP
-#undef STPL
-#undef STPA
-  if (next && swap_buffers) std::swap(d.pos, d.pos_tmp);
+  launch_step_kernel(d, p, A, a, a.ev_start, a.ev_stop);
+  if (p.next && a.swap_buffers) std::swap(d.pos, d.pos_tmp);
+}
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): the plan for a request under the
+// environment switches as they stand at this call.  req = langevin, next, ident, pair, angles, thermo, nvebit, lgbit, which,
+// check, cells; out = fused, the ten template arguments in k_step's order, bin, member_ranks, diag_bits, lds_pad, and whether
+// the dispatcher of launch_step holds the instantiation the plan names (its own look-up, nothing is launched)
+extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
+  StepRequest r;
+  r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
+  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10];
+  const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
+  const bool known = p.fused && with_step_kernel(p, [](auto) {});
+  const int v[16] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
+                     p.diag_bits, (int)p.lds_pad, known};
+  for (int k = 0; k < 16; k++) out[k] = v[k];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1286,15 +1239,11 @@ void upload_angle_table(DeviceState &d, const AngleTable &at) {
 void launch_angle(DeviceState &d, const AngleTable &at, bool eflag, bool overwrite) {
   if (d.apa <= 0) return;
   const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
-  if (overwrite)
-    hipLaunchKernelGGL((k_angle<false, true>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.ecap, d.box, at, d.pos, d.npad, d.eff_n,
-                       (const int4 *)d.eff_rec, d.f[0], d.f[1], d.f[2], d.partial_a, d.flags);
-  else if (eflag)
-    hipLaunchKernelGGL((k_angle<true>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.ecap, d.box, at, d.pos, d.npad, d.eff_n,
-                       (const int4 *)d.eff_rec, d.f[0], d.f[1], d.f[2], d.partial_a, d.flags);
-  else
-    hipLaunchKernelGGL((k_angle<false>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.ecap, d.box, at, d.pos, d.npad, d.eff_n,
-                       (const int4 *)d.eff_rec, d.f[0], d.f[1], d.f[2], d.partial_a, d.flags);
+  with_flags([&](auto E, auto O) {      // (the fused step kernel adds the forces of an `overwrite` launch to its own sums; no energies then)
+    if constexpr (!(E && O))
+      hipLaunchKernelGGL((k_angle<E, O>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.ecap, d.box, at, d.pos, d.npad, d.eff_n,
+                         (const int4 *)d.eff_rec, d.f[0], d.f[1], d.f[2], d.partial_a, d.flags);
+  }, eflag && !overwrite, overwrite);
 }
 void reduce_angle_partials(DeviceState &d, double *out8) {
   const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
@@ -1303,9 +1252,6 @@ void reduce_angle_partials(DeviceState &d, double *out8) {
   stream_sync(d);
   for (int k = 0; k < 8; k++) out8[k] = d.partial_h[k];
 }
-
-// can the fused step kernel take the angle forces of a run (launch_step's angle_forces)?  Needs the pair-style instantiations
-bool step_fuses_angles(const DeviceState &d, bool has_pair) { (void)d; return has_pair; }
 
 // sum the per-block partials in a fixed order (deterministic); the totals land in the table's spare row nb
 void reduce_partials(DeviceState &d, double *out16) {

@@ -732,37 +732,30 @@ void launch_lists(DeviceState &d, double cutneighsq, const double sl[4], bool ha
     const int *nsp = from_bpart ? (const int *)nullptr : d.nspecial;
     const int *spl = from_bpart ? (const int *)d.bpart : d.special;
     const int msp = from_bpart ? d.bpa : d.maxspecial;
-#define BUILD(NOSP, AS, FR)                                                                                        \
-  hipLaunchKernelGGL((k_build_neigh<NOSP, AS, FR>), dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.maxneigh, d.pos, d.posf, cutf, bandf, d.tag, d.map, \
-                     d.cell_start, d.gcell_start, ddcode, d.zlo_ext, d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0],  \
-                     d.cellinv[1], d.cellinv[2], d.box, cutneighsq, margin, nsp, spl, msp, sf1,  \
-                     sf2, sf3, d.bpart, d.bpa, d.bond_minimg ? nullptr : d.bshift, d.neigh, d.numneigh, d.flags, 0)
-    if (sf1 == 1 && sf2 == 1 && sf3 == 1) BUILD(true, false, false);
-    else if (d.flags_h[FLAG_SPECIAL_ASYM]) {      // sticky flag, read back at the last sync
-      PairOrder O{};
+    // one argument list for the list builds: symmetric special lists (NOSP: no special list at all), the build that follows
+    // the reference's pair order (sticky flag, read back at the last sync; `last` is its PairOrder) and the diagnostic one
+    auto build = [&](auto kernel, const int *nsp, const int *spl, int msp, int *counts, int *flags, auto last) {
+      hipLaunchKernelGGL(kernel, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.maxneigh, d.pos, d.posf, cutf, bandf, d.tag, d.map,
+                         d.cell_start, d.gcell_start, ddcode, d.zlo_ext, d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0],
+                         d.cellinv[1], d.cellinv[2], d.box, cutneighsq, margin, nsp, spl, msp, sf1,
+                         sf2, sf3, d.bpart, d.bpa, d.bond_minimg ? nullptr : d.bshift, d.neigh, counts, flags, last);
+    };
+    const bool nosp = sf1 == 1 && sf2 == 1 && sf3 == 1, asym = !nosp && d.flags_h[FLAG_SPECIAL_ASYM];
+    PairOrder O{};
+    if (asym) {
       O.crank = d.ident_order ? (const int *)nullptr : d.crank;
       O.newton = d.newton_pair;
       for (int k = 0; k < 3; k++) {
         O.lo[k] = d.box.lo[k]; O.hi[k] = d.box.hi[k]; O.prd[k] = d.box.prd[k]; O.half[k] = d.box.half[k];
         O.bininv[k] = d.ref_bininv[k]; O.nbin[k] = d.ref_nbin[k];
       }
-#define BUILD_ASYM(FR)                                                                                             \
-  hipLaunchKernelGGL((k_build_neigh_asym<FR>), dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.maxneigh, d.pos, d.posf, cutf, bandf, d.tag, d.map, \
-                     d.cell_start, d.gcell_start, ddcode, d.zlo_ext, d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0],  \
-                     d.cellinv[1], d.cellinv[2], d.box, cutneighsq, margin, nsp, spl, msp, sf1,  \
-                     sf2, sf3, d.bpart, d.bpa, d.bond_minimg ? nullptr : d.bshift, d.neigh, d.numneigh, d.flags, O)
-      if (frac) BUILD_ASYM(true); else BUILD_ASYM(false);
-#undef BUILD_ASYM
     }
-    else if (frac) BUILD(false, false, true);
-    else BUILD(false, false, false);
-#undef BUILD
-    if (const char *dg = getenv("LAMMPS_LE_DIAG_BUILD")) {   // diagnostics: extra launch, entry stores off, scratch counters
-      hipLaunchKernelGGL((k_build_neigh_diag<false, false, false>), dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.maxneigh, d.pos, d.posf, cutf, bandf, d.tag, d.map,
-                         d.cell_start, d.gcell_start, ddcode, d.zlo_ext, d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0],
-                         d.cellinv[1], d.cellinv[2], d.box, cutneighsq, margin, d.nspecial, d.special, d.maxspecial, sf1,
-                         sf2, sf3, d.bpart, d.bpa, d.bond_minimg ? nullptr : d.bshift, d.neigh, d.cell_of, d.flags + FLAG_AUX - FLAG_MAXNEIGH, atoi(dg) | 1);
-    }
+    with_flags([&](auto NOSP, auto AS, auto FR) {
+      if constexpr (AS && !NOSP) build(k_build_neigh_asym<FR>, nsp, spl, msp, d.numneigh, d.flags, O);
+      else if constexpr (!AS && !(NOSP && FR)) build(k_build_neigh<NOSP, false, FR>, nsp, spl, msp, d.numneigh, d.flags, 0);
+    }, nosp, asym, frac && !nosp);
+    if (const char *dg = getenv("LAMMPS_LE_DIAG_BUILD"))     // diagnostics: extra launch, entry stores off, scratch counters
+      build(k_build_neigh_diag<false, false, false>, d.nspecial, d.special, d.maxspecial, d.cell_of, d.flags + FLAG_AUX - FLAG_MAXNEIGH, atoi(dg) | 1);
   }
 }
 

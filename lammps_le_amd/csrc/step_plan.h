@@ -1,0 +1,89 @@
+// step_plan.h — which instantiation of the fused step kernel (k_step, kernels_md.hip) a time step takes, or that it takes
+// the unfused kernels.  Plain host code without a device in it: Engine::iterate states what it knows about the step
+// (StepRequest), plan_step answers, launch_step launches what the plan says.  The set of instantiations that exist is
+// step_variant_exists (kernels_md.hip); tests/test_step_plan_cpu.py holds the two against each other.
+#pragma once
+#include <cstdlib>
+
+namespace lmp_le {
+
+constexpr int AHEAD_MAX_BEADS = 64000;   // k_step: partner / first-stage loads issued ahead of their use up to this size
+constexpr int LPB4_MAX_BEADS = 50000;    // k_step: four lanes per bead up to this many (owned) beads, see k_step
+
+// Environment switches of the step kernel (experiments and tests).  Constructing a StepKnobs reads them - the one place
+// that does; Engine::iterate does it once per `run` command and the values hold for that run.
+inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+inline bool env_set(const char *name) { return getenv(name) != nullptr; }
+struct StepKnobs {
+  int lpb = env_int("LAMMPS_LE_LPB", 0);                              // 1 | 4: lanes per bead whatever the size (0: by size)
+  int lpb_max_n = env_int("LAMMPS_LE_LPB_MAX_N", LPB4_MAX_BEADS);     // four lanes per bead up to this many owned beads
+  int ahead_max_n = env_int("LAMMPS_LE_AHEAD_MAX_N", AHEAD_MAX_BEADS);   // loads issued ahead of their use up to this size
+  bool no_fuse = env_set("LAMMPS_LE_NO_FUSE");                        // unfused integrate / force / Langevin kernels
+  bool no_fused_thermo = env_set("LAMMPS_LE_NO_FUSED_THERMO");        // thermo steps through k_force<EFLAG> + k_langevin
+  bool no_fused_groups = env_set("LAMMPS_LE_NO_FUSED_GROUPS");        // fixes on groups through the unfused kernels
+  bool no_fused_bin = env_set("LAMMPS_LE_NO_FUSED_BIN");              // k_wrap_bin instead of binning in the step kernel
+  unsigned lds_pad = (unsigned)env_int("LAMMPS_LE_STEP_LDS_PAD", 0);  // bytes of unused dynamic LDS per workgroup, to lower the occupancy on purpose
+  int diag_step = env_int("LAMMPS_LE_DIAG_STEP", 0);                  // bits: an extra launch with parts switched off before the real one (launch_step)
+};
+
+// What the engine knows about the step.  langevin: a fix langevin acts; next: another step follows, its initial_integrate rides
+// along (no forces are stored); ident: the reference's local index of a bead is its ID - 1; pair: a pair style; angles: an
+// angle style is active; thermo: thermo output after this step, energies and virial are wanted; check: the displacement test
+// of Neighbor::check_distance is due; cells: the cell tables the binning writes are allocated
+struct StepRequest {
+  bool langevin = false, next = false, ident = false, pair = false, angles = false, thermo = false, check = false, cells = false;
+  int nvebit = 1, lgbit = 1; // group bits of fix nve / fix langevin (1 = all)
+  int which = -1;            // decomposed runs with halo / compute overlap: the phase this launch handles (-1: every bead)
+};
+
+struct StepPlan {
+  bool fused = false;        // false: not covered by the step kernel, take the unfused kernels (nothing below means anything)
+  // the template arguments of k_step
+  bool langevin = false, next = false, ident = false, pair = false;
+  int lpb = 1;
+  bool diag = false, ahead = false, ang = false, ef = false, grp = false;
+  bool bin = false;          // positions binned by this launch
+  bool member_ranks = false; // the draws go by the rank among the members of fix langevin's group, not by the canonical rank
+  int diag_bits = 0;         // != 0: the diagnostic launch <true, true, true, true, 1, DIAG> goes first, with these parts switched off
+  unsigned lds_pad = 0;
+  int which = -1, nvebit = 1, lgbit = 1;     // run-time arguments that come with the request
+  bool check = false;
+};
+
+inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, const StepKnobs &k) {
+  const StepPlan unfused;
+  StepPlan p;
+  if (k.no_fuse) return unfused;
+  // lanes per bead: 4 while the launch is latency-bound (few wavefronts per SIMD), 1 once it is throughput-bound
+  const bool want_lpb4 = k.lpb ? k.lpb == 4 : n_owned <= k.lpb_max_n;
+  const bool want_ahead = n_owned <= k.ahead_max_n;
+  p.langevin = r.langevin; p.next = r.next; p.ident = r.ident; p.pair = r.pair;
+  p.which = r.which; p.nvebit = r.nvebit; p.lgbit = r.lgbit; p.check = r.check; p.lds_pad = k.lds_pad;
+  p.grp = r.nvebit != 1 || r.lgbit != 1;
+  if (p.grp) {
+    // fix nve / fix langevin on a group: one lane per bead, ranks from a table; with an angle style only the throughput shape
+    // (the look-ahead shape of small systems has no group + angle instantiation); thermo steps take the unfused kernels
+    if (!r.pair || k.no_fused_groups || (r.angles && want_ahead) || r.thermo) return unfused;
+    p.ident = false; p.ang = r.angles;
+    p.member_ranks = r.lgbit != 1;
+  } else if (r.thermo) {
+    // a thermo step as ONE pass (the energy variant): one GPU, a pair style, the throughput shape of the kernel
+    if (!r.pair || decomposed || want_lpb4 || want_ahead || r.angles || k.no_fused_thermo || r.which >= 0) return unfused;
+    p.next = false; p.ef = true; p.check = false;
+  } else if (r.angles) {
+    if (!r.pair) return unfused;       // (no pair style: force kernel -> angle kernel -> integrate kernels)
+    p.ang = true; p.ahead = want_ahead;
+  } else if (want_lpb4) {
+    p.lpb = 4; p.ahead = true;
+  } else {
+    p.ahead = want_ahead;
+  }
+  p.fused = true;
+  // positions binned by this launch: single GPU, whole-step launch with a displacement test in it, one lane per bead (with
+  // four lanes per bead - small systems - it was measured slower than the separate k_wrap_bin: 62.2k vs 64.5k steps/s at 32k)
+  p.bin = p.check && p.next && !decomposed && r.which < 0 && p.lpb != 4 && !k.no_fused_bin && r.cells;
+  if (k.diag_step && r.langevin && r.next && r.ident && r.pair && r.which < 0 && p.lpb != 4 && !p.ef) p.diag_bits = k.diag_step;
+  return p;
+}
+
+}  // namespace lmp_le

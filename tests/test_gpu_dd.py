@@ -51,7 +51,8 @@ def run_ranks_local(world, system, script, tmp_path):
                        num_bond=lmp.gather("num_bond"), bond_type=lmp.gather("bond_type"), bond_atom=lmp.gather("bond_atom"),
                        nspecial=lmp.gather("nspecial"), special=lmp.gather("special"),
                        thermo=np.array([lmp.get_thermo(k) for k in ("temp", "epair", "emol", "etotal", "press", "bonds")]),
-                       neigh_pairs=np.array([lmp.stat("neigh_pairs")]), builds=np.array([lmp.stat("neigh_builds")]))
+                       neigh_pairs=np.array([lmp.stat("neigh_pairs")]), builds=np.array([lmp.stat("neigh_builds")]),
+                       steps_fused_group=np.array([lmp.stat("steps_fused_group")]), steps_unfused=np.array([lmp.stat("steps_unfused")]))
             if lmp.extract_setting("angle_per_atom") > 0:
                 res.update(num_angle=lmp.gather("num_angle"), angle_type=lmp.gather("angle_type"), angle_atom1=lmp.gather("angle_atom1"),
                            angle_atom2=lmp.gather("angle_atom2"), angle_atom3=lmp.gather("angle_atom3"),
@@ -250,7 +251,8 @@ def test_md_fixes_on_groups_across_slabs(tmp_path, world, case, monkeypatch):
     if case.endswith("+overlap"):        # (the group variant of the step kernel in its two-phase launches)
         monkeypatch.setenv("LAMMPS_LE_OVERLAP", "1")
         case = case[:-len("+overlap")]
-    if case.endswith("+unfused"):
+    unfused = case.endswith("+unfused")
+    if unfused:
         monkeypatch.setenv("LAMMPS_LE_NO_FUSED_GROUPS", "1")
         case = case[:-len("+unfused")]
     if case == "frozen-type":
@@ -271,6 +273,10 @@ def test_md_fixes_on_groups_across_slabs(tmp_path, world, case, monkeypatch):
     assert (r["image"] == o.image()).all()
     assert np.abs(r["thermo"][:5] - o.thermo()[:5]).max() < 1e-9
     assert r["builds"][0] == o.neigh_builds()
+    if unfused:          # (the switch is read at every run command: the steps of the last run took the unfused kernels)
+        assert r["steps_fused_group"][0] == 0 and r["steps_unfused"][0] > 0
+    elif case == "frozen-type":
+        assert r["steps_fused_group"][0] > 0
     if case == "frozen-type":
         frozen = types == 2
         assert np.array_equal(r["x"].reshape(n, 3)[frozen], o.x()[frozen])

@@ -156,6 +156,12 @@ def test_step_kernel_variants(tmp_path, env):
     to = o.thermo()
     for k in range(5):
         assert abs(res["thermo"][k] - to[k]) <= 1e-9 * max(1.0, abs(to[k]))
+    steps = dict(zip(("steps_fused", "steps_fused_group", "steps_fused_thermo", "steps_unfused"), res["steps"]))
+    assert steps["steps_fused"] > 0
+    if "LAMMPS_LE_NO_FUSED_THERMO" in env:
+        assert steps["steps_fused_thermo"] == 0
+    elif env == {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "0"}:     # plain: thermo every 25 over 60 steps - 25, 50, 60
+        assert steps["steps_fused_thermo"] == 3
 
 
 def test_chain_benchmark_golden(tmp_path):
@@ -263,7 +269,8 @@ def test_fixes_on_groups(tmp_path, case, monkeypatch):
     s = lattice_chain(n, nchains=3, seed=23, jitter=0.04, types=types)
     s["mass"] = [1.0, 1.0]
     head = CHAIN_SCRIPT
-    if case.endswith("+unfused"):        # (one fix nve + a pair style: the group variant of the fused step kernel unless switched off)
+    unfused = case.endswith("+unfused")
+    if unfused:        # (one fix nve + a pair style: the group variant of the fused step kernel unless switched off)
         monkeypatch.setenv("LAMMPS_LE_NO_FUSED_GROUPS", "1")
         case = case[:-len("+unfused")]
     if case.startswith("frozen-type"):   # every seventh bead is an anchor: neither integrated nor thermostatted
@@ -292,6 +299,13 @@ def test_fixes_on_groups(tmp_path, case, monkeypatch):
     for k, key in enumerate(("temp", "epair", "emol", "etotal", "press")):
         assert abs(p.get_thermo(key) - to[k]) <= 1e-9 * max(1.0, abs(to[k])), key
     assert p.stat("neigh_builds") == o.neigh_builds()
+    # the path the steps of the last run took (the switch is read at every run command, not once per process)
+    if unfused:
+        assert p.stat("steps_fused_group") == 0 and p.stat("steps_unfused") > 0
+    elif case in ("frozen-type", "langevin-all"):
+        assert p.stat("steps_fused_group") > 0
+    elif case == "two-nve":
+        assert p.stat("steps_fused") == 0
     if case.startswith("frozen-type"):
         frozen = types == 2
         assert np.array_equal(p.gather("x")[frozen], s["x"][frozen])

@@ -1,5 +1,5 @@
 """Runs one script on the product engine in a process of its own (test helper of test_gpu_md.py): the step kernel picks
-its variant from environment switches that are read once per process.
+its variant from environment switches.
 usage: variant_worker.py SYSTEM.pkl SCRIPT.txt OUT.npz"""
 import os
 import pickle
@@ -16,5 +16,6 @@ script = open(sys.argv[2]).read()
 p = run_product(script, system, os.path.dirname(sys.argv[3]))
 np.savez(sys.argv[3], x=p.gather("x"), v=p.gather("v"), image=p.gather("image"),
          thermo=np.array([p.get_thermo(k) for k in ("temp", "epair", "emol", "etotal", "press")]),
-         builds=np.array([p.stat("neigh_builds")]))
+         builds=np.array([p.stat("neigh_builds")]),
+         steps=np.array([p.stat(k) for k in ("steps_fused", "steps_fused_group", "steps_fused_thermo", "steps_unfused")]))
 p.close()
