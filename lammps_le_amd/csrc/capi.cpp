@@ -827,6 +827,7 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "nghost") return e->dev ? (double)e->dev->nghost : 0.0;
   if (k == "fene_warnings") return e->dev && e->dev->flags_h ? (double)e->dev->flags_h[FLAG_FENE_WARN] : 0.0;
   if (k == "host_downloads") return (double)e->host_downloads;          // whole-system downloads (Engine::download)
+  if (k == "device_bytes") return e->dev ? (double)e->dev->mem.device_bytes() : 0.0;   // device blocks this handle holds
   if (k == "subset_comm_bytes") return e->subset_comm_bytes;           // this rank's share of the subset calls' collectives
   return -1.0;
 }
@@ -840,6 +841,10 @@ extern "C" void lammps_le_test_ranmars(int seed, long long skip, int n, double *
   r.jump((uint64_t)skip);
   for (int i = 0; i < n; i++) out[i] = r.uniform();
 }
+
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): what all instances of this process
+// hold at this moment - out[0] device + pinned blocks, out[1] their bytes, out[2] streams + events (DevMem, device.h)
+extern "C" void lammps_le_test_live_resources(long long *out) { lmp_le::DevMem::live(out); }
 
 // test hook (not part of the reference surface, not declared in include/lammps_le.h): the neighbor list of the last build,
 // decoded on the host and named by TAGS.  Pair entries (i, j, special level bits of the word) go to itag / jtag / code,

@@ -87,11 +87,12 @@ int comm_rccl_selftest() {
   NCCL_CHECK(rccl.GetUniqueId(&id));
   ncclComm_t c = nullptr;
   NCCL_CHECK(rccl.CommInitRank(&c, 1, id, 0));
-  hipStream_t st;
-  HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  hipStream_t st = nullptr;
   int *d = nullptr;
   const int n = 1024;
-  HIP_CHECK(hipMalloc(&d, 4 * n * sizeof(int)));
+  DevMem mem;      // (frees both, also when a check throws)
+  mem.stream(st, "st", hipStreamNonBlocking);
+  DEV_ALLOC_RAW(mem, d, 4 * (size_t)n);
   std::vector<int> h(4 * n, 0);
   for (int i = 0; i < n; i++) h[i] = 3 * i - 1000;
   HIP_CHECK(hipMemcpyAsync(d, h.data(), 4 * n * sizeof(int), hipMemcpyHostToDevice, st));
@@ -109,8 +110,7 @@ int comm_rccl_selftest() {
     else if (h[2 * n + i] != h[i]) rc = 3;
     else if (h[3 * n + i] != h[i]) rc = 4;
   }
-  (void)hipFree(d);
-  (void)hipStreamDestroy(st);
+  mem.release_all();
   rccl.CommDestroy(c);
   return rc;
 }
@@ -383,10 +383,7 @@ void Comm::allgather_host(const void *send, void *recv, size_t bytes) {
   wait_stream(main_stream);
 }
 void Comm::ensure_bounce(size_t bytes) {
-  if (bytes <= bounce_bytes) return;
-  if (bounce) (void)hipFree(bounce);
-  HIP_CHECK(hipMalloc(&bounce, bytes));
-  bounce_bytes = bytes;
+  DEV_RESERVE(mem, bounce, bytes);
 }
 void Comm::ensure_hbuf(size_t bytes) {
   if (hbuf.size() < bytes) hbuf.resize(bytes);

@@ -56,11 +56,11 @@ struct Comm {
   std::vector<long> shm_sent, shm_rcvd;
   void shm_send(int dst, const void *buf, size_t bytes);
   void shm_recv(int src, void *buf, size_t bytes);
-  void *bounce = nullptr;
-  size_t bounce_bytes = 0;
+  char *bounce = nullptr;      // grow-only
   std::vector<char> hbuf;
   void ensure_bounce(size_t bytes);
   void ensure_hbuf(size_t bytes);
+  DevMem mem;      // owns bounce (the last member: destroyed first)
 };
 
 void comm_unique_id(char out[128]);

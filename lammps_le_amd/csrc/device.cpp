@@ -11,31 +11,82 @@
 
 namespace lmp_le {
 
-template <class T>
-static void dalloc(T *&p, size_t count) {
-  HIP_CHECK(hipMalloc((void **)&p, count * sizeof(T)));
+// process-wide, over all registries (test hook lammps_le_test_live_resources)
+static std::atomic<long long> live_blocks{0}, live_bytes{0}, live_handles{0};
+
+const DevMem::Rec *DevMem::find(void **field) const {
+  for (size_t k = recs.size(); k-- > 0;) if (recs[k].field == field) return &recs[k];
+  return nullptr;
+}
+void DevMem::adopt(void **field, size_t bytes, const char *name, Kind kind) {
+  recs.push_back({field, bytes, name, kind});
+  if (kind <= HOST) { live_blocks++; live_bytes += (long long)bytes; }
+  else live_handles++;
+}
+void DevMem::alloc_bytes(void **field, size_t bytes, const char *name, bool zero, unsigned host_flags, Kind kind) {
+  release_field(field);
+  if (kind == HOST) HIP_CHECK(hipHostMalloc(field, bytes, host_flags));
+  else HIP_CHECK(hipMalloc(field, bytes));
+  adopt(field, bytes, name, kind);
+  if (!zero) return;
   // null-stream memset + wait: the engine's streams are non-blocking, i.e. NOT ordered behind the null stream, and
   // a memset that is still pending when the first kernel writes the buffer would wipe that kernel's output
-  HIP_CHECK(hipMemset(p, 0, count * sizeof(T)));
+  HIP_CHECK(hipMemset(*field, 0, bytes));
   HIP_CHECK(hipStreamSynchronize(nullptr));
 }
-template <class T>
-static void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
+void DevMem::stream(hipStream_t &s, const char *name, unsigned flags, int priority) {
+  release(s);
+  HIP_CHECK(hipStreamCreateWithPriority(&s, flags, priority));      // (priority 0 = what hipStreamCreateWithFlags gives)
+  adopt((void **)&s, 0, name, STREAM);
 }
+void DevMem::event(hipEvent_t &e, const char *name, unsigned flags) {
+  release(e);
+  HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+  adopt((void **)&e, 0, name, EVENT);
+}
+void DevMem::release_field(void **field) {
+  const Rec *f = find(field);
+  if (!f) return;
+  const Rec r = *f;
+  recs.erase(recs.begin() + (f - recs.data()));
+  switch (r.kind) {
+    case DEVICE: (void)hipFree(*r.field); break;
+    case HOST: (void)hipHostFree(*r.field); break;
+    case STREAM: (void)hipStreamDestroy((hipStream_t)*r.field); break;
+    case EVENT: (void)hipEventDestroy((hipEvent_t)*r.field); break;
+  }
+  if (r.kind <= HOST) { live_blocks--; live_bytes -= (long long)r.bytes; }
+  else live_handles--;
+  *r.field = nullptr;
+}
+void DevMem::release_all(bool blocks_only) {
+  for (size_t k = recs.size(); k-- > 0;)
+    if (!blocks_only || recs[k].kind <= HOST) release_field(recs[k].field);
+}
+size_t DevMem::device_bytes() const {
+  size_t b = 0;
+  for (const Rec &r : recs) if (r.kind == DEVICE) b += r.bytes;
+  return b;
+}
+void DevMem::trace(const char *when, int rank) const {
+  const char *env = getenv("LAMMPS_LE_TRACE_ALLOC");
+  if (!env || atoi(env) == 0) return;
+  static const char *const kinds[] = {"device", "host", "stream", "event"};
+  for (const Rec &r : recs)
+    fprintf(stderr, "alloc[%s] rank %d %-24s %-6s %p %zu\n", when, rank, r.name, kinds[r.kind], *r.field, r.bytes);
+}
+void DevMem::live(long long out[3]) { out[0] = live_blocks; out[1] = live_bytes; out[2] = live_handles; }
 
 void dev_alloc_neigh(DeviceState &d, int maxneigh) {
   // (a bead's count word keeps the entries in 16 bits next to the number of bond entries: engine.h NN_BOND_SHIFT)
   if (maxneigh > NN_COUNT_MASK) throw LammpsError("Neighbor list overflow: more than 65535 neighbors per bead");
-  dfree(d.neigh);
   d.maxneigh = maxneigh;
-  dalloc(d.neigh, (size_t)maxneigh * d.npad);
+  DEV_ALLOC(d.mem, d.neigh, (size_t)maxneigh * d.npad);
 }
 
 void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxspecial, const Box &box,
                double cutneigh) {
-  if (!d.stream) HIP_CHECK(hipStreamCreateWithFlags(&d.stream, hipStreamNonBlocking));
+  if (!d.stream) d.mem.stream(d.stream, "d.stream", hipStreamNonBlocking);
   d.n = n;
   d.npad = ((n + 63) / 64) * 64 + 64;
   d.maxtag = maxtag;
@@ -47,26 +98,26 @@ void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxsp
   if (!d.dd) d.zlo_ext = box.lo[2];
   d.row_tile = (d.dd || getenv("LAMMPS_LE_NO_ROW_TILES")) ? 0 : ROW_TILE;      // (row_id relies on it being ROW_TILE or 0)
   size_t np = d.npad, nt = (size_t)maxtag + 2;
-  dalloc(d.pos, np); dalloc(d.pos_tmp, np); dalloc(d.xhold, np); dalloc(d.posf, np);
-  for (int k = 0; k < 3; k++) { dalloc(d.v[k], np); dalloc(d.v_tmp[k], np); dalloc(d.f[k], np); }
-  dalloc(d.tag, np); dalloc(d.tag_tmp, np);
-  dalloc(d.img, 3 * np); dalloc(d.img_tmp, 3 * np);
-  dalloc(d.map, nt); dalloc(d.type_t, nt); dalloc(d.crank, nt);
-  dalloc(d.num_bond, nt); dalloc(d.bond_type, nt * bpa); dalloc(d.bond_atom, nt * bpa);
-  dalloc(d.nspecial, nt * 3); dalloc(d.special, nt * (size_t)maxspecial);
-  dalloc(d.num_bond0, nt); dalloc(d.bond_type0, nt * bpa); dalloc(d.bond_atom0, nt * bpa);
+  DEV_ALLOC(d.mem, d.pos, np); DEV_ALLOC(d.mem, d.pos_tmp, np); DEV_ALLOC(d.mem, d.xhold, np); DEV_ALLOC(d.mem, d.posf, np);
+  for (int k = 0; k < 3; k++) { DEV_ALLOC(d.mem, d.v[k], np); DEV_ALLOC(d.mem, d.v_tmp[k], np); DEV_ALLOC(d.mem, d.f[k], np); }
+  DEV_ALLOC(d.mem, d.tag, np); DEV_ALLOC(d.mem, d.tag_tmp, np);
+  DEV_ALLOC(d.mem, d.img, 3 * np); DEV_ALLOC(d.mem, d.img_tmp, 3 * np);
+  DEV_ALLOC(d.mem, d.map, nt); DEV_ALLOC(d.mem, d.type_t, nt); DEV_ALLOC(d.mem, d.crank, nt);
+  DEV_ALLOC(d.mem, d.num_bond, nt); DEV_ALLOC(d.mem, d.bond_type, nt * bpa); DEV_ALLOC(d.mem, d.bond_atom, nt * bpa);
+  DEV_ALLOC(d.mem, d.nspecial, nt * 3); DEV_ALLOC(d.mem, d.special, nt * (size_t)maxspecial);
+  DEV_ALLOC(d.mem, d.num_bond0, nt); DEV_ALLOC(d.mem, d.bond_type0, nt * bpa); DEV_ALLOC(d.mem, d.bond_atom0, nt * bpa);
   if (d.apa > 0) {
-    dalloc(d.angle_pack, (size_t)ANGLE_PACK_COLS * nt * 4);
+    DEV_ALLOC(d.mem, d.angle_pack, (size_t)ANGLE_PACK_COLS * nt * 4);
     d.angle_pack_dirty = true;
-    dalloc(d.num_angle, nt); dalloc(d.angle_type, nt * d.apa); dalloc(d.angle_a1, nt * d.apa); dalloc(d.angle_a2, nt * d.apa);
-    dalloc(d.angle_a3, nt * d.apa);
+    DEV_ALLOC(d.mem, d.num_angle, nt); DEV_ALLOC(d.mem, d.angle_type, nt * d.apa); DEV_ALLOC(d.mem, d.angle_a1, nt * d.apa); DEV_ALLOC(d.mem, d.angle_a2, nt * d.apa);
+    DEV_ALLOC(d.mem, d.angle_a3, nt * d.apa);
     d.ecap = d.apa + 8;
-    dalloc(d.eff_n, np); dalloc(d.eff_rec, np * (size_t)d.ecap * 4);       // by the bead's physical index, records column-major
+    DEV_ALLOC(d.mem, d.eff_n, np); DEV_ALLOC(d.mem, d.eff_rec, np * (size_t)d.ecap * 4);       // by the bead's physical index, records column-major
   }
   if (maxtag >= (1 << BOND_TYPE_SHIFT)) throw LammpsError("MI355X engine: atom IDs must stay below 2^26");
   d.bond_pack_stride = ((1 + bpa) + 3) & ~3;
-  dalloc(d.bond_pack, nt * (size_t)d.bond_pack_stride);
-  for (int k = 0; k < 2; k++) dalloc(d.bond_pack_p[k], np * (size_t)d.bond_pack_stride);
+  DEV_ALLOC(d.mem, d.bond_pack, nt * (size_t)d.bond_pack_stride);
+  for (int k = 0; k < 2; k++) DEV_ALLOC(d.mem, d.bond_pack_p[k], np * (size_t)d.bond_pack_stride);
   d.bond_pack_dirty = true;
   d.bond_pack_p_valid = false;
   // cells of edge >= cutneigh
@@ -79,78 +130,71 @@ void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxsp
     d.cellinv[k] = d.ncell[k] / extent;
     d.ncells *= d.ncell[k];
   }
-  dalloc(d.cell_of, np); dalloc(d.cell_count, (size_t)d.ncells + 2); dalloc(d.cell_start, (size_t)d.ncells + 2);
-  dalloc(d.cell_fill, (size_t)d.ncells + 2); dalloc(d.scan_tmp, (size_t)d.ncells / 1024 + 2); dalloc(d.perm, np);
+  DEV_ALLOC(d.mem, d.cell_of, np); DEV_ALLOC(d.mem, d.cell_count, (size_t)d.ncells + 2); DEV_ALLOC(d.mem, d.cell_start, (size_t)d.ncells + 2);
+  DEV_ALLOC(d.mem, d.scan_tmp, (size_t)d.ncells / 1024 + 2); DEV_ALLOC(d.mem, d.perm, np);
   double vol = box.prd[0] * box.prd[1] * box.prd[2];
   double expect = (double)n / vol * 4.18879020478639 * cutneigh * cutneigh * cutneigh;
   int mn = (int)(expect * 1.5) + 24;
-  dalloc(d.numneigh, np);
-  dalloc(d.bpart, (size_t)std::max(bpa, 1) * np);   // >= 1 row: the step kernel loads before it masks
-  dalloc(d.bshift, np);
+  DEV_ALLOC(d.mem, d.numneigh, np);
+  DEV_ALLOC(d.mem, d.bpart, (size_t)std::max(bpa, 1) * np);   // >= 1 row: the step kernel loads before it masks
+  DEV_ALLOC(d.mem, d.bshift, np);
   dev_alloc_neigh(d, mn);
-  dalloc(d.pairtab, (size_t)6 * (ntypes + 1) * (ntypes + 1));
+  DEV_ALLOC(d.mem, d.pairtab, (size_t)6 * (ntypes + 1) * (ntypes + 1));
   d.nred_blocks = (n + 255) / 256 + 8;
-  dalloc(d.partial, (size_t)d.nred_blocks * 16);
-  dalloc(d.partial_a, (size_t)d.nred_blocks * 8);
-  dalloc(d.lgsum, ((size_t)d.nred_blocks + 1) * 16);
-  HIP_CHECK(hipHostMalloc((void **)&d.partial_h, (size_t)d.nred_blocks * 16 * sizeof(double)));
-  dalloc(d.flags, NFLAGS);
-  HIP_CHECK(hipHostMalloc((void **)&d.flags_h, (FLAG_SEQ_SLOT + 16) * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+  DEV_ALLOC(d.mem, d.partial, (size_t)d.nred_blocks * 16);
+  DEV_ALLOC(d.mem, d.partial_a, (size_t)d.nred_blocks * 8);
+  DEV_ALLOC(d.mem, d.lgsum, ((size_t)d.nred_blocks + 1) * 16);
+  d.mem.alloc_host(d.partial_h, (size_t)d.nred_blocks * 16, "d.partial_h");
+  DEV_ALLOC(d.mem, d.flags, NFLAGS);
+  d.mem.alloc_host(d.flags_h, FLAG_SEQ_SLOT + 16, "d.flags_h", hipHostMallocMapped | hipHostMallocCoherent);
   for (int k = 0; k < FLAG_SEQ_SLOT + 16; k++) d.flags_h[k] = 0;
   d.flags_seq = 0;
   d.bins_ready = false;
   d.cell_count_dirty = false;    // (freshly allocated arrays are zeroed)
   HIP_CHECK(hipHostGetDevicePointer((void **)&d.flags_h_dev, d.flags_h, 0));
   // LE fix scratch
-  dalloc(d.xt, nt);
-  dalloc(d.xht, nt);
-  for (int k = 0; k < 16; k++) dalloc(d.le_i[k], nt);
-  for (int k = 0; k < 2; k++) dalloc(d.le_d[k], nt);
-  dalloc(d.le_bits, 3 * (nt / 64 + 16));     // three masks: base / accepted pairs, partner below, partner above
-  dalloc(d.le_rng_state, (LE_MAX_FIXES + 1) * 100);      // (+ a scratch copy: chained barrier draws of fix extrusion, kernels_le.hip)
-  dalloc(d.le_draws, 2 * nt);      // (fix extrusion with chained barrier draws: up to four per listing, a listing per two beads)
-  dalloc(d.le_list, 4 * nt);
-  dalloc(d.le_scan, std::max(nt, (size_t)d.ncells + 2) / 1024 + 16);
+  DEV_ALLOC(d.mem, d.xt, nt);
+  DEV_ALLOC(d.mem, d.xht, nt);
+  for (int k = 0; k < 16; k++) DEV_ALLOC(d.mem, d.le_i[k], nt);
+  for (int k = 0; k < 2; k++) DEV_ALLOC(d.mem, d.le_d[k], nt);
+  DEV_ALLOC(d.mem, d.le_bits, 3 * (nt / 64 + 16));     // three masks: base / accepted pairs, partner below, partner above
+  DEV_ALLOC(d.mem, d.le_rng_state, (LE_MAX_FIXES + 1) * 100);      // (+ a scratch copy: chained barrier draws of fix extrusion, kernels_le.hip)
+  DEV_ALLOC(d.mem, d.le_draws, 2 * nt);      // (fix extrusion with chained barrier draws: up to four per listing, a listing per two beads)
+  DEV_ALLOC(d.mem, d.le_list, 4 * nt);
+  DEV_ALLOC(d.mem, d.le_scan, std::max(nt, (size_t)d.ncells + 2) / 1024 + 16);
+}
+
+bool dev_alloc_halo_window(DeviceState &d, size_t bytes) {
+  d.mem.release(d.halo_win);
+  // Uncached (else fine-grained) device memory, as RCCL allocates the buffers its peers write: a neighbour GPU stores into
+  // this window while kernels of this GPU are running, which ordinary (coarse-grained) device memory is only coherent
+  // for at kernel boundaries of ONE device - this GPU's L2 could keep serving a line of the previous exchange.
+  for (unsigned flag : {hipDeviceMallocUncached, hipDeviceMallocFinegrained}) {
+    if (hipExtMallocWithFlags((void **)&d.halo_win, bytes, flag) == hipSuccess) {
+      d.mem.adopt((void **)&d.halo_win, bytes, "d.halo_win", DevMem::DEVICE);
+      return true;
+    }
+    (void)hipGetLastError();
+    d.halo_win = nullptr;
+  }
+  return false;
 }
 
 void dd_fast_halo_free(DeviceState &d);   // kernels_dd.hip
+// What survives: configuration (dd, slab bounds, apa, lg_bit, newton_pair, ident_order, flags_seq ..), comm_stream with its
+// events and the kernel-timing events; those go with the registry, i.e. with the DeviceState.
 void dev_free(DeviceState &d) {
+  if (d.rng_stream) (void)hipStreamSynchronize(d.rng_stream);
+  if (d.stream) (void)hipStreamSynchronize(d.stream);
   dd_fast_halo_free(d);
-  if (d.rng_stream) {
-    (void)hipStreamSynchronize(d.rng_stream);
-    if (d.stream) (void)hipStreamSynchronize(d.stream);
-    for (int k = 0; k < 2; k++) { (void)hipEventDestroy(d.rng_done[k]); (void)hipEventDestroy(d.rng_consumed[k]); }
-    (void)hipStreamDestroy(d.rng_stream);
-    d.rng_stream = nullptr;
-  }
-  dfree(d.pos); dfree(d.pos_tmp); dfree(d.xhold); dfree(d.posf);
-  for (int k = 0; k < 3; k++) { dfree(d.v[k]); dfree(d.v_tmp[k]); dfree(d.f[k]); }
-  dfree(d.tag); dfree(d.tag_tmp); dfree(d.img); dfree(d.img_tmp);
-  dfree(d.map); dfree(d.type_t); dfree(d.crank);
-  dfree(d.num_bond); dfree(d.bond_type); dfree(d.bond_atom); dfree(d.nspecial); dfree(d.special); dfree(d.num_bond0); dfree(d.bond_type0); dfree(d.bond_atom0); dfree(d.bond_pack); dfree(d.bond_pack_p[0]); dfree(d.bond_pack_p[1]);
-  if (d.angtab_dev) { (void)hipFree(d.angtab_dev); d.angtab_dev = nullptr; }
-  dfree(d.gmask); dfree(d.lgrank);
-  dfree(d.cell_of); dfree(d.cell_count); dfree(d.cell_start); dfree(d.cell_fill); dfree(d.scan_tmp); dfree(d.perm);
-  dfree(d.neigh); dfree(d.numneigh); dfree(d.bpart); dfree(d.bshift); dfree(d.pairtab); dfree(d.partial); dfree(d.partial_a); dfree(d.lgsum);
-  dfree(d.angle_pack); dfree(d.num_angle); dfree(d.angle_type); dfree(d.angle_a1); dfree(d.angle_a2); dfree(d.angle_a3); dfree(d.eff_n); dfree(d.eff_rec);
-  if (d.partial_h) (void)hipHostFree(d.partial_h);
-  d.partial_h = nullptr;
-  dfree(d.flags);
-  if (d.flags_h) (void)hipHostFree(d.flags_h);
-  d.flags_h = nullptr;
-  dfree(d.rng_state); dfree(d.rng_jump); dfree(d.rng_buf[0]); dfree(d.rng_buf[1]); d.rng_out = nullptr;
-  dfree(d.rng_pool[0]); dfree(d.rng_pool[1]); dfree(d.rng_wstate); d.rng_W = 0; d.rng_batch_raw[0] = d.rng_batch_raw[1] = 0;
-  dfree(d.xt); dfree(d.xht);
-  if (d.capi_buf) { (void)hipFree(d.capi_buf); d.capi_buf = nullptr; d.capi_cap = 0; }
-  dfree(d.gcell_start); dfree(d.gcell_count); dfree(d.sendlist[0]); dfree(d.sendlist[1]); dfree(d.migbuf[0]);
-  dfree(d.migbuf[1]); dfree(d.migin); dfree(d.sendbuf); dfree(d.recvbuf); dfree(d.gdest); dfree(d.gtag_in); dfree(d.gone); dfree(d.phase); dfree(d.sendslot);
-  dfree(d.gather_send); d.gather_recv = nullptr; d.gather_cap = 0;
-  for (int k = 0; k < 16; k++) dfree(d.le_i[k]);
-  for (int k = 0; k < 2; k++) dfree(d.le_d[k]);
-  dfree(d.le_bits); dfree(d.le_rng_state); dfree(d.le_draws); dfree(d.le_list); dfree(d.le_scan);
-  sort_scratch_free(d);
-  if (d.stream) (void)hipStreamDestroy(d.stream);
-  d.stream = nullptr;
+  for (int k = 0; k < 2; k++) { d.mem.release(d.rng_done[k]); d.mem.release(d.rng_consumed[k]); }
+  d.mem.release(d.rng_stream);
+  d.mem.release_all(true);
+  d.mem.release(d.stream);
+  // words that describe freed memory
+  d.rng_out = nullptr; d.gather_recv = nullptr; d.halo_flag = nullptr;
+  d.rng_W = 0; d.rng_batch_raw[0] = d.rng_batch_raw[1] = 0;
+  d.bins_ready = false;
 }
 
 // flags reach the host through a mapped pinned page written by a one-wave kernel (a blit-copy of 64 bytes costs

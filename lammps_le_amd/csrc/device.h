@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <deque>
 #include <vector>
 
 #include <type_traits>
@@ -58,6 +59,49 @@ constexpr int CELL_XSPLIT = 4;
 
 constexpr int ANGLE_PACK_COLS = 4;
 constexpr int LE_MAX_FIXES = 16;   // extrusion / ex_load / ex_unload / bond/create / bond/break instances with a device RanMars state each
+
+// The one owner of what an instance holds on the device: device blocks, pinned host blocks, streams and events.  A record
+// names the resource by the ADDRESS of the pointer field that holds it (so it follows std::swap(d.pos, d.pos_tmp) and the
+// like), with its byte size (the capacity of a grow-only buffer), the field's name and its kind.  Allocating into a field
+// that holds a block of this registry frees that block first; releasing nulls the field.  Not copyable, one thread at a time.
+struct DevMem {
+  enum Kind { DEVICE, HOST, STREAM, EVENT };
+  struct Rec { void **field; size_t bytes; const char *name; Kind kind; };
+  std::vector<Rec> recs;
+  DevMem() = default;
+  DevMem(const DevMem &) = delete;
+  DevMem &operator=(const DevMem &) = delete;
+  ~DevMem() { release_all(); }
+  // `count` elements of device memory, zeroed unless told otherwise (null-stream memset + wait: see alloc_bytes)
+  template <class T> void alloc(T *&p, size_t count, const char *name, bool zero = true) { alloc_bytes((void **)&p, count * sizeof(T), name, zero, 0); }
+  // pinned host memory (`flags`: the runtime's, e.g. mapped | coherent), not zeroed
+  template <class T> void alloc_host(T *&p, size_t count, const char *name, unsigned flags = 0) { alloc_bytes((void **)&p, count * sizeof(T), name, false, flags, HOST); }
+  // grow-only: at least `count` elements, contents NOT kept and not zeroed; true when it (re-)allocated
+  template <class T> bool reserve(T *&p, size_t count, const char *name) {
+    if (count <= capacity(p)) return false;
+    alloc_bytes((void **)&p, count * sizeof(T), name, false, 0);
+    return true;
+  }
+  template <class T> size_t capacity(T *&p) const { const Rec *r = find((void **)&p); return r ? r->bytes / sizeof(T) : 0; }
+  // a block allocated by other means (freed like any block of its kind)
+  void adopt(void **field, size_t bytes, const char *name, Kind kind);
+  void stream(hipStream_t &s, const char *name, unsigned flags, int priority = 0);
+  void event(hipEvent_t &e, const char *name, unsigned flags);
+  template <class T> void release(T *&p) { release_field((void **)&p); }
+  void release_all(bool blocks_only = false);      // in reverse order of creation; every field is left null
+  size_t device_bytes() const;
+  void trace(const char *when, int rank) const;    // LAMMPS_LE_TRACE_ALLOC=1: every record to stderr
+  static void live(long long out[3]);              // process-wide: live blocks, their bytes, live streams + events
+
+ private:
+  const Rec *find(void **field) const;
+  void alloc_bytes(void **field, size_t bytes, const char *name, bool zero, unsigned host_flags, Kind kind = DEVICE);
+  void release_field(void **field);
+};
+// (the record's name is the field as written at the call)
+#define DEV_ALLOC(mem, field, count) (mem).alloc(field, count, #field)
+#define DEV_ALLOC_RAW(mem, field, count) (mem).alloc(field, count, #field, false)      // not zeroed
+#define DEV_RESERVE(mem, field, count) (mem).reserve(field, count, #field)
 
 struct DeviceState {
   hipStream_t stream = nullptr;
@@ -116,7 +160,7 @@ struct DeviceState {
   int ncell[3] = {0, 0, 0}, ncells = 0;
   int row_tile = 0;          // (y, z) rows of cells numbered in tiles of this edge (bin_inl.h row_id); 0 = z-major (decomposed runs)
   double cellinv[3] = {0, 0, 0};
-  int *cell_of = nullptr, *cell_count = nullptr, *cell_start = nullptr, *cell_fill = nullptr;
+  int *cell_of = nullptr, *cell_count = nullptr, *cell_start = nullptr;
   int *scan_tmp = nullptr, *perm = nullptr;
   int maxneigh = 0;
   int *neigh = nullptr;      // [maxneigh][npad] full list, special bits in the top 2 bits
@@ -197,7 +241,7 @@ struct DeviceState {
   bool bpart_fresh = false;                             // the permute pass of this rebuild has written the bond-partner table
   int *gmask = nullptr;                                 // [maxtag+2] group bits by tag (bit 0 = all); only when a fix acts on a group
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
-  void *angtab_dev = nullptr;                           // AngleTable in device memory (fused angle step)
+  char *angtab_dev = nullptr;                           // AngleTable in device memory (fused angle step)
   bool ghost_whole_shell = false;                       // every bead within the ghost cutoff of a face is sent (runs with an angle style)
   bool map_stale = true;                                // map[] was not left by a decomposed rebuild: fill it before the next one
   int nsend[2] = {0, 0}, nrecv[2] = {0, 0};
@@ -234,16 +278,21 @@ struct DeviceState {
   int *gtag_in = nullptr;                               // ghost tags in arrival order
   double *migbuf[2] = {nullptr, nullptr}, *migin = nullptr;   // migrating beads (MIG_W doubles each)
   double4 *xht = nullptr;                               // [maxtag+2] xhold by tag (LE fixes)
-  double *gather_send = nullptr, *gather_recv = nullptr;      // whole-system gathers
-  size_t gather_cap = 0;
-  void *sort_scratch = nullptr;   // kernels_sort.hip: key / value / temp buffers of the Atom::sort emulation
+  double *gather_send = nullptr, *gather_recv = nullptr;      // whole-system gathers (grow-only; gather_recv is a view into it)
+  // kernels_sort.hip: key / value / temp buffers of the Atom::sort emulation (grow-only)
+  unsigned long long *sort_keys[2] = {nullptr, nullptr};
+  int *sort_vals[2] = {nullptr, nullptr};
+  char *sort_temp = nullptr;
+  double *respa_flevel[8] = {nullptr};   // run_style respa: the forces of each level, by tag (Engine::respa_setup)
   Comm *comm_watch = nullptr;     // decomposed runs: host waits on the stream go through Comm::wait_stream (time-out + abort)
   // ---- kernel timing (HIP events on the launch stream) ----
-  std::vector<hipEvent_t> ev0, ev1;
+  std::deque<hipEvent_t> ev0, ev1;      // (a deque: the registry keeps the address of every element)
   size_t ev_used = 0;
   // ---- C-ABI subset calls (kernels_capi.hip): staging block of the K requested rows ----
-  void *capi_buf = nullptr;
-  size_t capi_cap = 0;
+  char *capi_buf = nullptr;     // grow-only
+  // owns every pointer (but the mapped peer windows), stream and event above.  The LAST member: destroyed first, while the
+  // fields its records point at are still there
+  DevMem mem;
 };
 
 // with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...): where the launchers turn run-time
@@ -259,6 +308,8 @@ template <class F, class... Rest> inline void with_flags(F &&f, bool b, Rest... 
 void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxspecial, const Box &box,
                double cutneigh);
 void dev_free(DeviceState &d);
+// d.halo_win: `bytes` of device memory that a peer GPU may store into while kernels of this one run; false: none to be had
+bool dev_alloc_halo_window(DeviceState &d, size_t bytes);
 void dev_alloc_neigh(DeviceState &d, int maxneigh);
 
 // integrate (kernels_md.hip)
@@ -302,7 +353,6 @@ void launch_lists(DeviceState &d, double cutneighsq, const double special_lj[4],
 
 // Atom::sort emulation (kernels_sort.hip): crank[tag] := rank in the reference's sorted local order
 void launch_atom_sort(DeviceState &d, const int nb[3], const double binv[3], bool by_tag = false);
-void sort_scratch_free(DeviceState &d);
 
 // rng (kernels_rng.hip)
 void rng_langevin_setup(DeviceState &d, RanMarsInt &host_rng, int natoms);

@@ -48,10 +48,9 @@ Engine::Engine(int argc, char **argv) {
 }
 
 Engine::~Engine() {
-  for (auto *&fl : respa_flevel) if (fl) { (void)hipFree(fl); fl = nullptr; }
   if (dev) {
     try { dev_free(*dev); } catch (...) {}
-    delete dev;
+    delete dev;      // (its registry lets go of what dev_free keeps: comm_stream, its events, the timing events)
   }
   if (comm) { try { comm->finalize(); } catch (...) {} delete comm; }
   if (logfile) fclose(logfile);
@@ -187,7 +186,7 @@ void Engine::upload() {
     d.apa = apa;
     dev_alloc(d, natoms, natoms, ntypes, bpa, maxspecial, box, cellcut);
     if (comm) comm->main_stream = d.stream;
-    if (d.dd) { dd_alloc(d, world); dd_fast_halo_setup(d, *comm); }
+    if (d.dd) { dd_alloc(d, world); dd_fast_halo_setup(d, *comm); d.mem.trace("dd", rank); }
     for (auto &f : fixes)
       if (auto *l = dynamic_cast<FixLangevin *>(f.get())) l->dev_ready = false;
   }
@@ -259,7 +258,7 @@ void Engine::upload() {
         for (int k = 0; k < n; k++) { const int i = order[k]; if (gmask[i] & lgbit) lr[i + 1] = m++; }
         langevin_members = m;
       }
-      if (!d.gmask) { HIP_CHECK(hipMalloc((void **)&d.gmask, nt * sizeof(int))); HIP_CHECK(hipMalloc((void **)&d.lgrank, nt * sizeof(int))); }
+      DEV_RESERVE(d.mem, d.gmask, nt); DEV_RESERVE(d.mem, d.lgrank, nt);
       up(d.gmask, gm.data(), nt * sizeof(int));
       up(d.lgrank, lr.data(), nt * sizeof(int));
     }
@@ -341,6 +340,7 @@ void Engine::upload() {
   HIP_CHECK(hipStreamSynchronize(d.stream));
   dev_current = true;
   host_current = true;
+  if (realloc) d.mem.trace("upload", rank);
 }
 
 void Engine::download() {
@@ -656,9 +656,8 @@ static bool timed_begin(Engine *e) {
   long c = e->ktime_counter++;
   if (!e->kernel_timing || d.ev_used >= 4096 || (c % e->ktime_every) != 0) return false;
   if (d.ev0.size() <= d.ev_used) {
-    hipEvent_t a, b;
-    HIP_CHECK(hipEventCreate(&a)); HIP_CHECK(hipEventCreate(&b));
-    d.ev0.push_back(a); d.ev1.push_back(b);
+    d.ev0.push_back(nullptr); d.ev1.push_back(nullptr);
+    d.mem.event(d.ev0.back(), "d.ev0[k]", hipEventDefault); d.mem.event(d.ev1.back(), "d.ev1[k]", hipEventDefault);
   }
   return true;
 }
@@ -1075,24 +1074,22 @@ void Engine::respa_setup() {                                   // Respa::setup (
   for (int l = top - 1; l >= 0; l--) respa_step[l] = respa_step[l + 1] / respa_loop[l];
   const size_t need = 3 * (size_t)(d.maxtag + 2);
   for (int l = 0; l <= top; l++) {
-    if (respa_flevel[l] && respa_flevel_n != need) { HIP_CHECK(hipFree(respa_flevel[l])); respa_flevel[l] = nullptr; }
-    if (!respa_flevel[l]) HIP_CHECK(hipMalloc((void **)&respa_flevel[l], need * sizeof(double)));
-    HIP_CHECK(hipMemsetAsync(respa_flevel[l], 0, need * sizeof(double), d.stream));
+    DEV_RESERVE(d.mem, d.respa_flevel[l], need);
+    HIP_CHECK(hipMemsetAsync(d.respa_flevel[l], 0, need * sizeof(double), d.stream));
   }
-  respa_flevel_n = need;
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
   for (int l = 0; l <= top; l++) {
     respa_level_forces(l);
-    launch_flevel_copy(d, respa_flevel[l], true, false);
+    launch_flevel_copy(d, d.respa_flevel[l], true, false);
   }
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
   if (lg) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array
-    launch_flevel_copy(d, respa_flevel[top], false, false);
+    launch_flevel_copy(d, d.respa_flevel[top], false, false);
     langevin_post_force(this, lg, false);
-    launch_flevel_copy(d, respa_flevel[top], true, false);
+    launch_flevel_copy(d, d.respa_flevel[top], true, false);
   }
   compute_forces(true);              // energies and virial of the initial state for the thermo line (forces are reloaded per level)
   last_thermo = eval_thermo();
@@ -1111,7 +1108,7 @@ void Engine::respa_recurse(int l, bool last) {
   const double triggersq = 0.25 * skin * skin;
   FixLangevin *lg = the_langevin(this);
   const std::vector<int> nbits = nve_bits(this);                              // (fix nve on a group: the respa variants use the same mask)
-  launch_flevel_copy(d, respa_flevel[l], false, false);                       // copy_flevel_f
+  launch_flevel_copy(d, d.respa_flevel[l], false, false);                       // copy_flevel_f
   const TypeTables ttl = level_tables(this, respa_step[l]);
   for (int iloop = 0; iloop < respa_loop[l]; iloop++) {
     const bool last_here = last && iloop == respa_loop[l] - 1;
@@ -1129,7 +1126,7 @@ void Engine::respa_recurse(int l, bool last) {
       const bool sort_due = sortfreq > 0 && ntimestep >= nextsort;
       stamp();
       // decomposed: beads may change owner in this rebuild - the level tables are completed on every rank first
-      if (world > 1) for (int q = 0; q <= top; q++) dd_gather_rows3(d, *comm, respa_flevel[q]);
+      if (world > 1) for (int q = 0; q <= top; q++) dd_gather_rows3(d, *comm, d.respa_flevel[q]);
       reneighbor(false, sort_due);
       stamp(T_NEIGH);
     } else if (l == 0 && world > 1) {
@@ -1146,7 +1143,7 @@ void Engine::respa_recurse(int l, bool last) {
     for (int k = 0; k < nnve; k++) launch_final_integrate(d, ttl, nbits[k]); // final_integrate_respa (src/fix_nve.cpp:159-163)
     stamp(T_MODIFY);
   }
-  launch_flevel_copy(d, respa_flevel[l], true, false);                        // copy_f_flevel
+  launch_flevel_copy(d, d.respa_flevel[l], true, false);                        // copy_f_flevel
 }
 void Engine::respa_iterate(long nsteps) {                                    // Respa::run (:544-575)
   DeviceState &d = *dev;
@@ -1166,8 +1163,8 @@ void Engine::respa_iterate(long nsteps) {                                    // 
         print_thermo(last_thermo);
       }
       // sum_flevel_f (:817-843): the total force of the step, for outputs that read it
-      launch_flevel_copy(d, respa_flevel[0], false, false);
-      for (int l = 1; l < respa_levels; l++) launch_flevel_copy(d, respa_flevel[l], false, true);
+      launch_flevel_copy(d, d.respa_flevel[0], false, false);
+      for (int l = 1; l < respa_levels; l++) launch_flevel_copy(d, d.respa_flevel[l], false, true);
       if (dump_now && !dumps.empty() && dump_due(ntimestep)) write_dumps(ntimestep);
       if (restart_now) write_periodic_restart(ntimestep);
       stamp(T_OUTPUT);

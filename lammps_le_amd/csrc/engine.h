@@ -274,8 +274,6 @@ class Engine {
   // path of unfused kernels (round 3: also decomposed): what the LE fixes' post_integrate_respa hooks need
   int respa_levels = 0, respa_loop[8] = {1, 1, 1, 1, 1, 1, 1, 1}, respa_level_bond = 0, respa_level_pair = 0, respa_level_angle = 0;
   double respa_step[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  double *respa_flevel[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // device, by tag
-  size_t respa_flevel_n = 0;
   void respa_setup();                          // Respa::setup
   void respa_iterate(long n);                  // Respa::run
   void respa_recurse(int ilevel, bool last);   // Respa::recurse

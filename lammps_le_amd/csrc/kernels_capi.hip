@@ -101,12 +101,8 @@ __global__ __launch_bounds__(CAPI_BLOCK) void k_subset_scatter(int K, int prop, 
 
 // device staging buffer: [K ids][K*count values (8-byte aligned)][K found]
 static char *capi_staging(DeviceState &d, size_t bytes) {
-  if (bytes > d.capi_cap) {
-    if (d.capi_buf) HIP_CHECK(hipFree(d.capi_buf));
-    d.capi_cap = std::max(bytes, (size_t)1 << 16);
-    HIP_CHECK(hipMalloc(&d.capi_buf, d.capi_cap));
-  }
-  return (char *)d.capi_buf;
+  if (bytes > d.mem.capacity(d.capi_buf)) DEV_RESERVE(d.mem, d.capi_buf, std::max(bytes, (size_t)1 << 16));
+  return d.capi_buf;
 }
 static size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
 

@@ -314,14 +314,13 @@ __global__ __launch_bounds__(BLOCK) void k_dd_scatter_xt(long total, const doubl
 // =============================================================================================
 static void ensure_gather(DeviceState &d, size_t doubles_per_rank, int world) {
   size_t need = doubles_per_rank * (size_t)(world + 1);
-  if (need > d.gather_cap) {
+  if (need > d.mem.capacity(d.gather_send)) {
     // Regrow: no stream of this process may still touch the old buffer.  A peer rank that is a thread of this process copies
     // out of it on ITS stream (comm.cpp local_exchange); the sender's host has seen that copy enqueued (the acknowledgement)
     // but not finished, so the whole device is drained before the buffer goes: this is the one buffer of a decomposed run
     // that is re-allocated while a run is live.  (The crash records of the in-process transport are not this: comm.cpp.)
-    if (d.gather_send) { HIP_CHECK(hipDeviceSynchronize()); (void)hipFree(d.gather_send); }
-    HIP_CHECK(hipMalloc(&d.gather_send, need * sizeof(double)));
-    d.gather_cap = need;
+    if (d.gather_send) HIP_CHECK(hipDeviceSynchronize());
+    DEV_RESERVE(d.mem, d.gather_send, need);
   }
   d.gather_recv = d.gather_send + doubles_per_rank;      // (per call: the two gathers differ in their row width)
 }
@@ -465,8 +464,8 @@ void dd_fast_halo_free(DeviceState &d) {
     if (d.peer_base[k] && !(k == 1 && d.peer_base[1] == d.peer_base[0])) (void)hipIpcCloseMemHandle(d.peer_base[k]);
     d.peer_base[k] = nullptr; d.peer_win[k] = nullptr; d.peer_flag[k] = nullptr;
   }
-  if (d.halo_win) (void)hipFree(d.halo_win);
-  d.halo_win = nullptr; d.halo_flag = nullptr; d.halo_cap = 0;
+  d.mem.release(d.halo_win);
+  d.halo_flag = nullptr; d.halo_cap = 0;
   d.fast_halo = d.halo_mapped = false; d.packed_peer = 0; d.halo_seq = 0;
 }
 
@@ -485,18 +484,7 @@ void dd_fast_halo_setup(DeviceState &d, Comm &comm) {
   const size_t bytes = halo_flag_offset(d.halo_cap) + 256;
   long bad = 0;
   PeerInfo mine{};
-  // Uncached (else fine-grained) device memory, as RCCL allocates the buffers its peers write: a neighbour GPU stores into
-  // this window while kernels of this GPU are running, which ordinary (coarse-grained) device memory is only coherent
-  // for at kernel boundaries of ONE device - this GPU's L2 could keep serving a line of the previous exchange.
-  if (hipExtMallocWithFlags((void **)&d.halo_win, bytes, hipDeviceMallocUncached) != hipSuccess) {
-    (void)hipGetLastError();
-    d.halo_win = nullptr;
-    if (hipExtMallocWithFlags((void **)&d.halo_win, bytes, hipDeviceMallocFinegrained) != hipSuccess) {
-      (void)hipGetLastError();
-      d.halo_win = nullptr;
-      bad = 1;
-    }
-  }
+  if (!dev_alloc_halo_window(d, bytes)) bad = 1;
   if (!bad) {
     HIP_CHECK(hipMemset(d.halo_win, 0, bytes));
     HIP_CHECK(hipStreamSynchronize(nullptr));
@@ -551,29 +539,26 @@ void dd_fast_halo_setup(DeviceState &d, Comm &comm) {
 
 void dd_alloc(DeviceState &d, int world) {
   size_t np = d.npad;
-  auto al = [](auto *&p, size_t bytes) {
-    if (p) (void)hipFree(p);
-    HIP_CHECK(hipMalloc((void **)&p, bytes));
-    HIP_CHECK(hipMemset(p, 0, bytes));
-    HIP_CHECK(hipStreamSynchronize(nullptr));   // see dalloc (device.cpp)
-  };
-  al(d.gcell_start, ((size_t)d.ncells + 2) * sizeof(int));
-  al(d.gcell_count, ((size_t)d.ncells + 2) * sizeof(int));
-  for (int k = 0; k < 2; k++) { al(d.sendlist[k], np * sizeof(int)); al(d.sendlist_alt[k], np * sizeof(int)); al(d.migbuf[k], np * MIG_W * sizeof(double) / 4 + 1024); }
-  d.map_stale = true;
-  al(d.migin, np * MIG_W * sizeof(double) / 2 + 1024);
-  al(d.sendbuf, np * sizeof(double4));
-  al(d.recvbuf, np * sizeof(double4));
-  al(d.gdest, np * sizeof(int));
-  al(d.gone, np * sizeof(int));
-  al(d.phase, np);
-  al(d.sendslot, np * sizeof(int));
-  if (!d.comm_stream) {
-    HIP_CHECK(hipStreamCreateWithFlags(&d.comm_stream, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&d.ev_phase1, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&d.ev_halo, hipEventDisableTiming));
+  DEV_ALLOC(d.mem, d.gcell_start, (size_t)d.ncells + 2);
+  DEV_ALLOC(d.mem, d.gcell_count, (size_t)d.ncells + 2);
+  for (int k = 0; k < 2; k++) {
+    DEV_ALLOC(d.mem, d.sendlist[k], np); DEV_ALLOC(d.mem, d.sendlist_alt[k], np);
+    DEV_ALLOC(d.mem, d.migbuf[k], np * MIG_W / 4 + 128);      // (MIG_W doubles per bead + 1024 bytes)
   }
-  al(d.gtag_in, np * sizeof(int));
+  d.map_stale = true;
+  DEV_ALLOC(d.mem, d.migin, np * MIG_W / 2 + 128);
+  DEV_ALLOC(d.mem, d.sendbuf, np);
+  DEV_ALLOC(d.mem, d.recvbuf, np);
+  DEV_ALLOC(d.mem, d.gdest, np);
+  DEV_ALLOC(d.mem, d.gone, np);
+  DEV_ALLOC(d.mem, d.phase, np);
+  DEV_ALLOC(d.mem, d.sendslot, np);
+  if (!d.comm_stream) {
+    d.mem.stream(d.comm_stream, "d.comm_stream", hipStreamNonBlocking);
+    d.mem.event(d.ev_phase1, "d.ev_phase1", hipEventDisableTiming);
+    d.mem.event(d.ev_halo, "d.ev_halo", hipEventDisableTiming);
+  }
+  DEV_ALLOC(d.mem, d.gtag_in, np);
   (void)world;
 }
 

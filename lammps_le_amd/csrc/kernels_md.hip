@@ -1232,7 +1232,7 @@ __global__ __launch_bounds__(BLOCK) void k_angle(int n, int ecap, Box box, Angle
 }
 // the coefficient table in device memory, for the fused step (kernel arguments of k_step are not to be touched)
 void upload_angle_table(DeviceState &d, const AngleTable &at) {
-  if (!d.angtab_dev) HIP_CHECK(hipMalloc((void **)&d.angtab_dev, sizeof(AngleTable)));
+  DEV_RESERVE(d.mem, d.angtab_dev, sizeof(AngleTable));
   HIP_CHECK(hipMemcpyAsync(d.angtab_dev, &at, sizeof(AngleTable), hipMemcpyHostToDevice, d.stream));
   HIP_CHECK(hipStreamSynchronize(d.stream));      // (`at` is the caller's object)
 }

@@ -178,11 +178,8 @@ static const int *rng_rank_table(const DeviceState &d) {
   return d.ident_order ? (const int *)nullptr : d.crank;
 }
 static void rng_free_batch(DeviceState &d) {
-  for (int k = 0; k < 2; k++) if (d.rng_pool[k]) { (void)hipFree(d.rng_pool[k]); d.rng_pool[k] = nullptr; }
-  if (d.rng_wstate) { (void)hipFree(d.rng_wstate); d.rng_wstate = nullptr; }
-  if (d.rng_need) { (void)hipFree(d.rng_need); d.rng_need = nullptr; }
-  if (d.rng_late) { (void)hipFree(d.rng_late); d.rng_late = nullptr; }
-  for (int k = 0; k < 2; k++) if (d.rng_gen[k]) { (void)hipFree(d.rng_gen[k]); d.rng_gen[k] = nullptr; }
+  for (int k = 0; k < 2; k++) { d.mem.release(d.rng_pool[k]); d.mem.release(d.rng_gen[k]); }
+  d.mem.release(d.rng_wstate); d.mem.release(d.rng_need); d.mem.release(d.rng_late);
   d.rng_batch_raw[0] = d.rng_batch_raw[1] = 0;
 }
 
@@ -192,10 +189,10 @@ void rng_langevin_setup(DeviceState &d, RanMarsInt &host_rng, int natoms) {
     // lowest priority: the generator is a background trickle and must not delay the step kernels' workgroups
     int prio_lo = 0, prio_hi = 0;
     HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-    HIP_CHECK(hipStreamCreateWithPriority(&d.rng_stream, hipStreamNonBlocking, prio_lo));
+    d.mem.stream(d.rng_stream, "d.rng_stream", hipStreamNonBlocking, prio_lo);
     for (int k = 0; k < 2; k++) {
-      HIP_CHECK(hipEventCreateWithFlags(&d.rng_done[k], hipEventDisableTiming));
-      HIP_CHECK(hipEventCreateWithFlags(&d.rng_consumed[k], hipEventDisableTiming));
+      d.mem.event(d.rng_done[k], "d.rng_done[k]", hipEventDisableTiming);
+      d.mem.event(d.rng_consumed[k], "d.rng_consumed[k]", hipEventDisableTiming);
     }
   }
   HIP_CHECK(hipStreamSynchronize(d.rng_stream));
@@ -231,14 +228,13 @@ void rng_langevin_setup(DeviceState &d, RanMarsInt &host_rng, int natoms) {
       if (skip && !getenv("LAMMPS_LE_RNG_SEGMENTS")) { d.rng_seglen = std::min<long long>(65535, total); d.rng_nseg = S = (int)((total + d.rng_seglen - 1) / d.rng_seglen); }
       d.rng_seglen = (d.rng_seglen + 2) / 3 * 3;       // a bead's three draws never straddle two segments
       d.rng_nseg = S = (int)((total + d.rng_seglen - 1) / d.rng_seglen);
-      for (int k = 0; k < 2; k++) HIP_CHECK(hipMalloc(&d.rng_pool[k], (size_t)W * total * sizeof(uint32_t)));
-      HIP_CHECK(hipMalloc(&d.rng_wstate, 3 * (size_t)W * S * 97 * sizeof(uint32_t)));
-      HIP_CHECK(hipMalloc(&d.rng_need, 2 * (size_t)S * sizeof(int)));      // one per pool
-      HIP_CHECK(hipMalloc(&d.rng_late, 2 * (size_t)S * sizeof(int)));
-      for (int k = 0; k < 2; k++) HIP_CHECK(hipMalloc(&d.rng_gen[k], (size_t)S * sizeof(int)));
-      HIP_CHECK(hipMemset(d.rng_late, 0, 2 * (size_t)S * sizeof(int)));
-      if (d.rng_jump) { (void)hipFree(d.rng_jump); d.rng_jump = nullptr; }
-      HIP_CHECK(hipMalloc(&d.rng_jump, 3 * 97 * sizeof(uint32_t)));
+      // (none of these is zeroed but rng_late: the pools alone are up to 64 GiB, and every word is written before it is read)
+      for (int k = 0; k < 2; k++) DEV_ALLOC_RAW(d.mem, d.rng_pool[k], (size_t)W * total);
+      DEV_ALLOC_RAW(d.mem, d.rng_wstate, 3 * (size_t)W * S * 97);
+      DEV_ALLOC_RAW(d.mem, d.rng_need, 2 * (size_t)S);      // one per pool
+      DEV_ALLOC(d.mem, d.rng_late, 2 * (size_t)S);
+      for (int k = 0; k < 2; k++) DEV_ALLOC_RAW(d.mem, d.rng_gen[k], (size_t)S);
+      DEV_ALLOC_RAW(d.mem, d.rng_jump, 3 * 97);
       // a segment's window goes from the end of the segment to the start of the same segment W calls later; a skipped
       // segment's from its start (third polynomial)
       uint32_t a[3 * 97];
@@ -259,13 +255,9 @@ void rng_langevin_setup(DeviceState &d, RanMarsInt &host_rng, int natoms) {
   d.rng_B = natoms < 200000 ? 192 : 3072;
   if (getenv("LAMMPS_LE_RNG_B")) d.rng_B = std::min(RNG_MAXB, std::max(96, atoi(getenv("LAMMPS_LE_RNG_B"))));
   d.rng_nblocks = (int)((total + d.rng_B - 1) / d.rng_B);
-  if (d.rng_state) { (void)hipFree(d.rng_state); d.rng_state = nullptr; }
-  if (d.rng_jump) { (void)hipFree(d.rng_jump); d.rng_jump = nullptr; }
-  for (int k = 0; k < 2; k++) if (d.rng_buf[k]) { (void)hipFree(d.rng_buf[k]); d.rng_buf[k] = nullptr; }
-  d.rng_out = nullptr;
-  HIP_CHECK(hipMalloc(&d.rng_state, (size_t)d.rng_nblocks * 97 * sizeof(uint32_t)));
-  HIP_CHECK(hipMalloc(&d.rng_jump, 97 * sizeof(uint32_t)));
-  for (int k = 0; k < 2; k++) HIP_CHECK(hipMalloc(&d.rng_buf[k], (size_t)total * sizeof(uint32_t)));
+  DEV_ALLOC_RAW(d.mem, d.rng_state, (size_t)d.rng_nblocks * 97);
+  DEV_ALLOC_RAW(d.mem, d.rng_jump, 97);
+  for (int k = 0; k < 2; k++) DEV_ALLOC_RAW(d.mem, d.rng_buf[k], (size_t)total);
   d.rng_cur = 0; d.rng_out = d.rng_buf[0]; d.rng_ahead = false;
   std::vector<uint32_t> st((size_t)d.rng_nblocks * 97);
   RanMarsInt r = host_rng;   // positioned at the first draw of the next call
@@ -523,12 +515,12 @@ extern "C" int lammps_le_test_device_ranmars(int seed, long long skip, int count
   try {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return 1;
-    DeviceState d;
-    HIP_CHECK(hipStreamCreate(&d.stream));
-    HIP_CHECK(hipMalloc(&d.le_rng_state, 300 * sizeof(uint32_t)));
-    uint32_t *draws; int *cnt;
-    HIP_CHECK(hipMalloc(&draws, (size_t)count * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc(&cnt, sizeof(int)));
+    uint32_t *draws = nullptr; int *cnt = nullptr;
+    DeviceState d;      // (its registry frees all of this, also when a check throws)
+    d.mem.stream(d.stream, "d.stream", hipStreamDefault);
+    DEV_ALLOC_RAW(d.mem, d.le_rng_state, 300);
+    DEV_ALLOC_RAW(d.mem, draws, (size_t)count);
+    DEV_ALLOC_RAW(d.mem, cnt, 1);
     RanMarsInt r; r.seed(seed); r.jump((uint64_t)skip);
     le_rng_upload(d, 1, r);
     std::vector<uint32_t> h(count);
@@ -541,7 +533,6 @@ extern "C" int lammps_le_test_device_ranmars(int seed, long long skip, int count
       done += n;
     }
     for (int i = 0; i < count; i++) out[i] = h[i] * (1.0 / 16777216.0);
-    (void)hipFree(draws); (void)hipFree(cnt); (void)hipFree(d.le_rng_state); (void)hipStreamDestroy(d.stream);
     return 0;
   } catch (...) { return 2; }
 }

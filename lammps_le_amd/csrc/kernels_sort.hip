@@ -51,72 +51,33 @@ __global__ __launch_bounds__(BLOCK) void k_sort_member_ranks(int n, const int *_
   if (r < n) lgrank[sorted_tags[r]] = flag[r] ? scan[r] : 0;
 }
 
-struct SortScratch {
-  unsigned long long *keys[2] = {nullptr, nullptr};
-  int *vals[2] = {nullptr, nullptr};
-  void *temp = nullptr;
-  size_t temp_bytes = 0;
-  int cap = 0;
-};
-static SortScratch &scratch_of(DeviceState &d) {
-  if (!d.sort_scratch) d.sort_scratch = new SortScratch();
-  return *(SortScratch *)d.sort_scratch;
-}
-void sort_scratch_free(DeviceState &d) {
-  if (!d.sort_scratch) return;
-  SortScratch &s = *(SortScratch *)d.sort_scratch;
-  for (int k = 0; k < 2; k++) { if (s.keys[k]) (void)hipFree(s.keys[k]); if (s.vals[k]) (void)hipFree(s.vals[k]); }
-  if (s.temp) (void)hipFree(s.temp);
-  delete &s;
-  d.sort_scratch = nullptr;
-}
-
 // crank[tag] := position of the bead in the reference's freshly sorted local order.  Positions must be the wrapped ones
 // of the reneighbor this sort belongs to (the caller runs it right behind Engine::reneighbor).
 // `by_tag` (decomposed runs): every rank sorts ALL beads from the all-gathered positions by tag (d.xt, filled by
 // dd_gather_positions right before), so that the replicated `crank` is the one-rank order on every rank.
 void launch_atom_sort(DeviceState &d, const int nb[3], const double binv[3], bool by_tag) {
   const int n = by_tag ? d.maxtag : d.n;
-  SortScratch &s = scratch_of(d);
-  if (s.cap < n) {
-    for (int k = 0; k < 2; k++) {
-      if (s.keys[k]) (void)hipFree(s.keys[k]);
-      if (s.vals[k]) (void)hipFree(s.vals[k]);
-      HIP_CHECK(hipMalloc((void **)&s.keys[k], (size_t)d.npad * sizeof(unsigned long long)));
-      HIP_CHECK(hipMalloc((void **)&s.vals[k], (size_t)d.npad * sizeof(int)));
-    }
-    s.cap = d.npad;
-    if (s.temp) (void)hipFree(s.temp);
-    s.temp = nullptr; s.temp_bytes = 0;
-  }
+  for (int k = 0; k < 2; k++) { DEV_RESERVE(d.mem, d.sort_keys[k], (size_t)d.npad); DEV_RESERVE(d.mem, d.sort_vals[k], (size_t)d.npad); }      // (n <= npad)
   const unsigned long long ntot = (unsigned long long)d.maxtag + 1;
   const unsigned long long nbins = (unsigned long long)nb[0] * nb[1] * nb[2];
   int bits = 1;
   while (bits < 64 && ((nbins * ntot) >> bits) != 0ull) bits++;
   const int grid = (n + BLOCK - 1) / BLOCK;
   hipLaunchKernelGGL(k_sort_keys, dim3(grid), dim3(BLOCK), 0, d.stream, n, by_tag ? d.xt + 1 : d.pos, by_tag ? (const int *)nullptr : d.tag, d.crank, d.box, nb[0], nb[1], nb[2],
-                     binv[0], binv[1], binv[2], ntot, s.keys[0], s.vals[0]);
+                     binv[0], binv[1], binv[2], ntot, d.sort_keys[0], d.sort_vals[0]);
   size_t need = 0;
-  HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, s.keys[0], s.keys[1], s.vals[0], s.vals[1], (size_t)n, 0u, (unsigned)bits, d.stream));
-  if (need > s.temp_bytes) {
-    if (s.temp) (void)hipFree(s.temp);
-    HIP_CHECK(hipMalloc(&s.temp, need));
-    s.temp_bytes = need;
-  }
-  HIP_CHECK(rocprim::radix_sort_pairs(s.temp, need, s.keys[0], s.keys[1], s.vals[0], s.vals[1], (size_t)n, 0u, (unsigned)bits, d.stream));
-  hipLaunchKernelGGL(k_sort_ranks, dim3(grid), dim3(BLOCK), 0, d.stream, n, s.vals[1], d.crank);
+  HIP_CHECK(rocprim::radix_sort_pairs(nullptr, need, d.sort_keys[0], d.sort_keys[1], d.sort_vals[0], d.sort_vals[1], (size_t)n, 0u, (unsigned)bits, d.stream));
+  DEV_RESERVE(d.mem, d.sort_temp, need);
+  HIP_CHECK(rocprim::radix_sort_pairs(d.sort_temp, need, d.sort_keys[0], d.sort_keys[1], d.sort_vals[0], d.sort_vals[1], (size_t)n, 0u, (unsigned)bits, d.stream));
+  hipLaunchKernelGGL(k_sort_ranks, dim3(grid), dim3(BLOCK), 0, d.stream, n, d.sort_vals[1], d.crank);
   if (d.lg_grouped) {      // (keys[0] / vals[0] are free again: flags and their scan)
-    int *flag = s.vals[0], *scan = reinterpret_cast<int *>(s.keys[0]);
-    hipLaunchKernelGGL(k_sort_member_flags, dim3(grid), dim3(BLOCK), 0, d.stream, n, s.vals[1], d.gmask, d.lg_bit, flag);
+    int *flag = d.sort_vals[0], *scan = reinterpret_cast<int *>(d.sort_keys[0]);
+    hipLaunchKernelGGL(k_sort_member_flags, dim3(grid), dim3(BLOCK), 0, d.stream, n, d.sort_vals[1], d.gmask, d.lg_bit, flag);
     size_t need2 = 0;
     HIP_CHECK(rocprim::exclusive_scan(nullptr, need2, flag, scan, 0, (size_t)n, rocprim::plus<int>(), d.stream));
-    if (need2 > s.temp_bytes) {
-      if (s.temp) (void)hipFree(s.temp);
-      HIP_CHECK(hipMalloc(&s.temp, need2));
-      s.temp_bytes = need2;
-    }
-    HIP_CHECK(rocprim::exclusive_scan(s.temp, need2, flag, scan, 0, (size_t)n, rocprim::plus<int>(), d.stream));
-    hipLaunchKernelGGL(k_sort_member_ranks, dim3(grid), dim3(BLOCK), 0, d.stream, n, s.vals[1], flag, scan, d.lgrank);
+    DEV_RESERVE(d.mem, d.sort_temp, need2);
+    HIP_CHECK(rocprim::exclusive_scan(d.sort_temp, need2, flag, scan, 0, (size_t)n, rocprim::plus<int>(), d.stream));
+    hipLaunchKernelGGL(k_sort_member_ranks, dim3(grid), dim3(BLOCK), 0, d.stream, n, d.sort_vals[1], flag, scan, d.lgrank);
   }
 }
 

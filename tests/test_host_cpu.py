@@ -595,3 +595,36 @@ def test_oracle_one_level_respa_is_verlet():
     d = run_oracle(base + "run_style respa 3 2 2 bond 1 pair 3\nrun 40\n", s)      # an empty middle level changes nothing
     assert 1e-6 < np.abs(a.x() - c.x()).max() < 0.1
     assert np.abs(c.x() - d.x()).max() < 1e-9
+
+
+def test_device_resources_have_one_owner():
+    """Device and pinned memory, streams and events are created and destroyed in device.cpp alone (the registry DevMem):
+    no other source of the engine calls the runtime for them."""
+    calls = re.compile(r"\bhip(?:Malloc|Free|HostMalloc|HostFree|ExtMallocWithFlags|StreamCreate\w*|StreamDestroy|EventCreate\w*|EventDestroy)\b")
+    allowed = {
+        # the event ring of the in-process transport: per thread, never destroyed while the process lives, because a waiter
+        # of another rank's stream may still hold a record of any of them (the comment at ring_event says why)
+        ("comm.cpp", "ring_event", "hipEventCreateWithFlags"),
+        # the event that marks the main stream's position for the generator stream: one per thread, shared by every
+        # instance the thread drives, so it cannot belong to one instance's registry
+        ("kernels_rng.hip", "rng_mark_event", "hipEventCreateWithFlags"),
+    }
+    src = os.path.join(ROOT, "lammps_le_amd", "csrc")
+    files = sorted(f for f in os.listdir(src) if f.endswith((".cpp", ".hip", ".h")))
+    assert "device.cpp" in files and len(files) >= 18
+    found, bad = set(), []
+    for f in files:
+        if f == "device.cpp":
+            continue
+        func = ""
+        for no, ln in enumerate(open(os.path.join(src, f)), 1):
+            m = re.match(r"^(?:static\s+)?[\w:<>\*&\s]+?\b(\w+)\([^;]*\)\s*\{\s*$", ln)      # the enclosing function's opening line
+            if m and not ln.startswith((" ", "\t")):
+                func = m.group(1)
+            for c in calls.findall(ln):
+                if (f, func, c) in allowed:
+                    found.add((f, func, c))
+                else:
+                    bad.append("%s:%d %s" % (f, no, c))
+    assert not bad, bad
+    assert found == allowed                  # an exception that no longer exists leaves the list
