@@ -818,6 +818,8 @@ double lammps_le_stat(void *handle, const char *name) {
   }
   if (k == "special_asym") return e->dev ? (double)e->dev->flags_h[FLAG_SPECIAL_ASYM] : 0.0;   // some 1-2 list lost an entry its partner still has (sticky)
   if (k == "halo_fused") return e->dev && e->dev->fast_halo && e->dev->halo_fused ? 1.0 : 0.0;   // counters + window copy in one launch
+  if (k == "halo_sent_both") return e->dev ? (double)e->dev->nsend_both : 0.0;   // beads of this rank in both send lists at the last rebuild
+  if (k == "halo_pack_launches") return e->dev ? (double)e->dev->halo_pack_launches : 0.0;   // k_dd_pack launches of dd_halo so far
   if (k == "halo_window_exchanges") return e->dev ? (double)e->dev->halo_seq : 0.0;   // per-step halos that went through the peer windows
   if (k == "pair_kernel_ms") return e->kstat_ms;
   if (k == "pair_kernel_launches") return (double)e->kstat_n;
@@ -840,6 +842,16 @@ extern "C" void lammps_le_test_ranmars(int seed, long long skip, int n, double *
   r.seed(seed);
   r.jump((uint64_t)skip);
   for (int i = 0; i < n; i++) out[i] = r.uniform();
+}
+
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): the width rule of the z-slab
+// decomposition (device.h slab_rule) without a device.  Returns 0 = accepted, 1 = thinner than one ghost cutoff, 2 = thinner
+// than two pair shells, 3 = ghost shells overlap; the error text Engine::upload would throw goes to msg (cap bytes).
+extern "C" int lammps_le_test_slab_rule(double prd_z, int world, double cutneighmax, double comm_cutoff, char *msg, int cap) {
+  std::string why;
+  const int code = (int)lmp_le::slab_rule(prd_z, world, cutneighmax, comm_cutoff, why);
+  if (msg && cap > 0) { strncpy(msg, why.c_str(), (size_t)cap - 1); msg[cap - 1] = 0; }
+  return code;
 }
 
 // test hook (not part of the reference surface, not declared in include/lammps_le.h): what all instances of this process

@@ -7,8 +7,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <deque>
+#include <string>
 #include <vector>
 
 #include <type_traits>
@@ -40,8 +42,8 @@ enum FlagSlot {
   FLAG_SPECIAL_ASYM = 11,
   FLAG_RECV_UP = 12,    // decomposition: counts received from the upper / lower slab neighbour
   FLAG_RECV_DN = 13,
-  FLAG_SEND_BOTH = 14,
-  FLAG_GHOST_MIXED = 15, // decomposition: ghosts from below and above are not two separate blocks of the cell order  // decomposition: some bead is in both send lists (slab barely two shells thick)   // some bead's 1-2 list lost an entry its partner still has (see dev_special_remove12)
+  FLAG_COUNT_BOTH = 14, // decomposition: beads of this rank in BOTH send lists at the last rebuild (slabs below two ghost cutoffs)
+  FLAG_GHOST_MIXED = 15, // (unused)
   FLAG_RNG_MISS = 16,    // decomposition: an owned bead's Langevin draws lie in a stream segment this rank skipped (kernels_rng.hip)
   NFLAGS = 24
 };
@@ -51,6 +53,36 @@ enum DevErr {
   ERR_SPECIAL = 5, ERR_COUNT_MISMATCH = 6, ERR_NONFINITE = 7, ERR_SPECIAL_SCRATCH = 8, ERR_GHOST_ORDER = 9,
   ERR_HALO_TIMEOUT = 10, ERR_ANGLES = 11
 };
+
+// z-slab decomposition: may `world` ranks share a box `prd_z` tall?  w = prd_z / world is a slab's width, cutghost =
+// max(neighbor cutoff, comm_modify cutoff) the depth of a ghost shell.  Three conditions, in the order they are tested:
+//   w >= cutghost                 every ghost of a rank lives on a DIRECT neighbour (thinner slabs would need multi-hop ghosts)
+//   w >= 2 * cutneighmax          a bead within the pair shell (rc + skin) of one face is outside the pair shell of the other:
+//                                 the two ranks that read it as a pair neighbor are distinct from each other and from its owner
+//   w + 2 * cutghost <= prd_z     the shells [lo - cutghost, lo) and [hi, hi + cutghost) of a rank do not overlap around the
+//                                 period (for two ranks this is w >= 2 * cutghost: thin slabs mean three or more ranks)
+// Between one and two ghost cutoffs a bead can lie in the ghost shell of BOTH faces: it is then in both send lists
+// (k_dd_borders, DeviceState::sendboth).  Host only; the one place the rule lives (Engine::upload, lammps_le_test_slab_rule).
+enum SlabRule { SLAB_OK = 0, SLAB_BELOW_GHOST_CUTOFF = 1, SLAB_BELOW_PAIR_SHELLS = 2, SLAB_SHELLS_OVERLAP = 3 };
+inline SlabRule slab_rule(double prd_z, int world, double cutneighmax, double comm_cutoff, std::string &msg) {
+  const double w = prd_z / world, cutghost = std::max(cutneighmax, comm_cutoff);
+  msg.clear();
+  if (w < cutghost) {
+    msg = "slab thinner than one ghost cutoff (slab width " + std::to_string(w) + ", ghost cutoff " + std::to_string(cutghost) +
+          "): use fewer GPUs or a smaller comm_modify cutoff";
+    return SLAB_BELOW_GHOST_CUTOFF;
+  }
+  if (w < 2.0 * cutneighmax) {
+    msg = "slab thinner than two pair shells (slab width " + std::to_string(w) + ", neighbor cutoff " + std::to_string(cutneighmax) +
+          "): use fewer GPUs";
+    return SLAB_BELOW_PAIR_SHELLS;
+  }
+  if (w + 2.0 * cutghost > prd_z) {
+    msg = "ghost shells of a slab overlap: box too small for this many GPUs";
+    return SLAB_SHELLS_OVERLAP;
+  }
+  return SLAB_OK;
+}
 
 // Neighbor cells are cutneigh wide in y and z and cutneigh / CELL_XSPLIT wide in x (the fastest index of the cell
 // order): the 2*CELL_XSPLIT+1 x-cells a bead has to look at are still ONE contiguous index range per (y,z) row, but
@@ -250,8 +282,12 @@ struct DeviceState {
   // halo / compute overlap: beads that are sent to a neighbour or read a ghost form phase 1 of a step, the rest
   // (phase 0) is computed while the ghost positions of the next step travel on comm_stream
   unsigned char *phase = nullptr;                       // [npad]
-  int *sendslot = nullptr;                              // [npad] slot of a border bead in its send list (bit 30 = upper list), -1 = none
-  bool sendslot_fallback = false;                       // some bead sits in both send lists: pack with the kernel instead
+  int *sendslot = nullptr;                              // [npad] slot of a border bead in its send list (bit 30 = upper list), -1 = none,
+                                                        // <= -2: in both lists, entry -2 - sendslot[p] of sendboth
+  int *sendboth = nullptr;                              // [2 * npad] {slot in the lower list, slot in the upper list} of a bead in both:
+                                                        // a view, sendslot + npad (the step kernel finds it without an argument of its own)
+  int nsend_both = 0;                                   // ... and how many there are since the last rebuild (lammps_le_stat)
+  long halo_pack_launches = 0;                          // k_dd_pack launches of dd_halo since the handle was opened (lammps_le_stat)
   bool direct_recv = false;                             // send lists are in the receiver's sorted ghost order: a halo lands in place
   bool packed_ahead = false;                            // the step kernel already wrote the border beads' new positions into sendbuf
   hipStream_t comm_stream = nullptr;

@@ -172,9 +172,8 @@ void Engine::upload() {
     d.slab_hi = d.slab_lo + w;
     d.cutghost = std::max(cutneighmax, comm_cutoff);
     d.zlo_ext = d.slab_lo - d.cutghost;
-    if (w < 2.0 * d.cutghost)
-      throw LammpsError("slab thinner than two ghost cutoffs: use fewer GPUs or a smaller comm_modify cutoff");
-    if (w + 2.0 * d.cutghost > box.prd[2]) throw LammpsError("ghost shells of a slab overlap: box too small for this many GPUs");
+    std::string why;      // (slabs down to one ghost cutoff: device.h slab_rule)
+    if (slab_rule(box.prd[2], world, cutneighmax, comm_cutoff, why) != SLAB_OK) throw LammpsError(why);
   }
   if (!realloc)
     for (int k = 0; k < 3; k++) {
@@ -462,7 +461,7 @@ static void check_device_error(Engine *e, DeviceState &d) {
     case ERR_HALO_TIMEOUT: msg = "a neighbouring rank did not deliver its halo in time (peer window exchange)"; break;
     case ERR_SPECIAL_SCRATCH: msg = "Special list size exceeded in fix bond/create"; break;
     case ERR_ANGLES: msg = "Fix ex_load induced too many angles/dihedrals/impropers per atom"; break;
-    case ERR_GHOST_ORDER: msg = "internal: ghost blocks of a slab interleave (slab thinner than two ghost shells?)"; break;
+    case ERR_GHOST_ORDER: msg = "internal: a ghost's place in the cell order lies outside the block of the neighbour that sent it"; break;
   }
   (void)e;
   throw LammpsError(msg);

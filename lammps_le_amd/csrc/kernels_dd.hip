@@ -138,6 +138,11 @@ __global__ __launch_bounds__(BLOCK) void k_dd_arrive(int narr, int base, int npa
 // of a slab per step over xGMI, against 23 % here — the forces are the same because only bond partners are ever
 // looked up beyond the pair shell.  Slots: wave-aggregated atomics; the receiver sorts its ghosts by cell and ID,
 // so the list order is free.
+// A slab between one and two ghost cutoffs thick (device.h slab_rule): a bead can lie within the ghost cutoff of BOTH faces and
+// is then in both lists - a bonded far-shell bead now and then, most beads of the slab in a whole-shell (angle) run.  Such a
+// bead's sendslot word is <= -2 and names entry -2 - sendslot[p] of the side table `both` ({slot below, slot above}, slots
+// from a third wave-aggregated counter); a bead in one list keeps the one-word encoding, so nothing but these beads pays
+// the second load.
 __global__ __launch_bounds__(BLOCK) void k_dd_borders(int n, const double4 *__restrict__ pos, Box box, double slab_lo,
                                                       double width, double cutpair, double cutghost, int bpa,
                                                       const int *__restrict__ tag, const int *__restrict__ map,
@@ -145,7 +150,7 @@ __global__ __launch_bounds__(BLOCK) void k_dd_borders(int n, const double4 *__re
                                                       const int *__restrict__ bond_atom, int *__restrict__ list_dn,
                                                       int *__restrict__ list_up, int *__restrict__ flags,
                                                       unsigned char *__restrict__ phase, int *__restrict__ sendslot,
-                                                      RngValidateArgs V, int whole_shell) {
+                                                      int *__restrict__ both, RngValidateArgs V, int whole_shell) {
   int p = blockIdx.x * BLOCK + threadIdx.x;
   bool active = p < n;
   if (active && V.late) rng_validate_bead(V, tag[p], flags);      // do this rank's pools hold the draws of what it owns now?
@@ -163,12 +168,12 @@ __global__ __launch_bounds__(BLOCK) void k_dd_borders(int n, const double4 *__re
   }
   int sd = wave_append(dn, &flags[FLAG_COUNT_A]);
   int su = wave_append(up, &flags[FLAG_COUNT_B]);
+  int sb = wave_append(dn && up, &flags[FLAG_COUNT_BOTH]);
   if (dn) list_dn[sd] = p;
   if (up) list_up[su] = p;
-  // the fused step kernel packs a border bead's new position itself (no pack launch per step); a slab is at least two
-  // ghost shells thick, so a bead is in at most one list - if it ever is in both, -2 makes the halo fall back to packing
-  if (active) sendslot[p] = (dn && up) ? -2 : dn ? sd : up ? (su | (1 << 30)) : -1;
-  if (dn && up) flags[FLAG_ERROR] = ERR_GHOST_ORDER;
+  if (dn && up) { both[2 * sb] = sd; both[2 * sb + 1] = su; }
+  // the fused step kernel packs a border bead's new position itself (no pack launch per step)
+  if (active) sendslot[p] = (dn && up) ? -2 - sb : dn ? sd : up ? (su | (1 << 30)) : -1;
   // sent beads are phase 1: a bead with a ghost NEIGHBOR lies within the pair shell of a face and is therefore sent;
   // the bond-table kernel adds the few beads whose bond partner is a ghost
   if (active) phase[p] = (dn || up) ? 1 : 0;
@@ -262,13 +267,15 @@ __global__ __launch_bounds__(BLOCK) void k_dd_ghost_place(int m, int base, int n
 __global__ __launch_bounds__(BLOCK) void k_dd_reorder_sends(int m0, int m1, const int *__restrict__ rel,
                                                             const int *__restrict__ list0, const int *__restrict__ list1,
                                                             int *__restrict__ new0, int *__restrict__ new1,
-                                                            int *__restrict__ sendslot) {
+                                                            int *__restrict__ sendslot, int *__restrict__ both) {
   int k = blockIdx.x * BLOCK + threadIdx.x;
   if (k >= m0 + m1) return;
   bool up = k >= m0;
   int p = up ? list1[k - m0] : list0[k], r = rel[k];
   (up ? new1 : new0)[r] = p;
-  if (sendslot[p] >= 0) sendslot[p] = up ? (r | (1 << 30)) : r;
+  const int sl = sendslot[p];
+  if (sl >= 0) sendslot[p] = up ? (r | (1 << 30)) : r;
+  else if (sl <= -2) both[2 * (-2 - sl) + (up ? 1 : 0)] = r;      // in both lists: this list's half of its pair (word unchanged)
 }
 __global__ __launch_bounds__(BLOCK) void k_fill_int(int n, int *a, int v) {
   int i = blockIdx.x * BLOCK + threadIdx.x;
@@ -552,7 +559,8 @@ void dd_alloc(DeviceState &d, int world) {
   DEV_ALLOC(d.mem, d.gdest, np);
   DEV_ALLOC(d.mem, d.gone, np);
   DEV_ALLOC(d.mem, d.phase, np);
-  DEV_ALLOC(d.mem, d.sendslot, np);
+  DEV_ALLOC(d.mem, d.sendslot, 3 * np);      // one word per bead, then the pairs of the beads in both lists
+  d.sendboth = d.sendslot + np;
   if (!d.comm_stream) {
     d.mem.stream(d.comm_stream, "d.comm_stream", hipStreamNonBlocking);
     d.mem.event(d.ev_phase1, "d.ev_phase1", hipEventDisableTiming);
@@ -575,7 +583,7 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
   const int migcap = (int)(((size_t)d.npad * MIG_W / 4) / MIG_W);
   // counts travel rank-to-rank on the device and reach the host together with this rank's own counters: one
   // host synchronisation per phase (migration, borders) instead of three
-  const unsigned counters = (1u << FLAG_COUNT_A) | (1u << FLAG_COUNT_B) | (1u << FLAG_NDRAW) | (1u << FLAG_SEND_BOTH);
+  const unsigned counters = (1u << FLAG_COUNT_A) | (1u << FLAG_COUNT_B) | (1u << FLAG_NDRAW) | (1u << FLAG_COUNT_BOTH);
   auto swap_counts = [&](int slot_dn, int slot_up) {
     comm.exchange(st, {{d.flags + slot_dn, sizeof(int), dn_rank}, {d.flags + slot_up, sizeof(int), up_rank}},
                   {{d.flags + FLAG_RECV_UP, sizeof(int), up_rank}, {d.flags + FLAG_RECV_DN, sizeof(int), dn_rank}});
@@ -618,11 +626,16 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
   // ---- 3. borders ----
   hipLaunchKernelGGL(k_dd_borders, dim3(nb), dim3(BLOCK), 0, st, n, d.pos, d.box, d.slab_lo, width,
                      std::min(sqrt(cutneighsq), d.cutghost), d.cutghost, d.bpa, d.tag, d.map, d.num_bond, d.bond_atom,
-                     d.sendlist[0], d.sendlist[1], d.flags, d.phase, d.sendslot, rng_validate_args(d), d.ghost_whole_shell ? 1 : 0);
+                     d.sendlist[0], d.sendlist[1], d.flags, d.phase, d.sendslot, d.sendboth, rng_validate_args(d), d.ghost_whole_shell ? 1 : 0);
   swap_counts(FLAG_COUNT_A, FLAG_COUNT_B);
   d.nsend[0] = d.flags_h[FLAG_COUNT_A];
   d.nsend[1] = d.flags_h[FLAG_COUNT_B];
-  d.sendslot_fallback = false;
+  d.nsend_both = d.flags_h[FLAG_COUNT_BOTH];
+  // (a bead in both lists counts twice; the staging buffer, the tag buffer and the order exchange hold npad records)
+  if ((size_t)d.nsend[0] + (size_t)d.nsend[1] > (size_t)d.npad)
+    throw LammpsError("halo overflow: the two send lists of this rank (" + std::to_string(d.nsend[0]) + " + " +
+                      std::to_string(d.nsend[1]) + " beads, " + std::to_string(d.nsend_both) + " of them in both) exceed the staging buffer (" +
+                      std::to_string(d.npad) + ")");
   d.nrecv[0] = d.flags_h[FLAG_RECV_DN];
   d.nrecv[1] = d.flags_h[FLAG_RECV_UP];
   d.nghost = d.nrecv[0] + d.nrecv[1];
@@ -665,11 +678,11 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
                        {rel_out + d.nrecv[1], (size_t)d.nrecv[0] * sizeof(int), dn_rank}},
                   {{rel_in, (size_t)d.nsend[0] * sizeof(int), dn_rank},
                    {rel_in + d.nsend[0], (size_t)d.nsend[1] * sizeof(int), up_rank}});
-    // (slabs are at least two ghost shells thick, so the two blocks cannot interleave and no bead is in both send
-    // lists; FLAG_GHOST_MIXED / FLAG_SEND_BOTH would be an internal error and are reported with the build's flags)
+    // (a slab is wider than a cell, so the ghosts from below and from above fill different z layers of the local grid and
+    // the two blocks cannot interleave; a bead in both send lists gets its place in each block: sendboth)
     if (nsall) {
       hipLaunchKernelGGL(k_dd_reorder_sends, dim3((nsall + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d.nsend[0], d.nsend[1],
-                         rel_in, d.sendlist[0], d.sendlist[1], d.sendlist_alt[0], d.sendlist_alt[1], d.sendslot);
+                         rel_in, d.sendlist[0], d.sendlist[1], d.sendlist_alt[0], d.sendlist_alt[1], d.sendslot, d.sendboth);
       std::swap(d.sendlist[0], d.sendlist_alt[0]);
       std::swap(d.sendlist[1], d.sendlist_alt[1]);
     }
@@ -715,6 +728,7 @@ void dd_halo(DeviceState &d, Comm &comm, hipStream_t st, const double4 *src, dou
     d.halo_seq = seq;
     d.packed_peer = 0;
     if (d.halo_verify && nsall + d.nghost > 0) {
+      d.halo_pack_launches++;
       hipLaunchKernelGGL(k_dd_pack, dim3((std::max(nsall, 1) + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d.nsend[0], d.nsend[1],
                          d.sendlist[0], d.sendlist[1], src, d.sendbuf);
       comm.exchange(st, {{d.sendbuf, (size_t)d.nsend[0] * sizeof(double4), dn_rank},
@@ -727,6 +741,7 @@ void dd_halo(DeviceState &d, Comm &comm, hipStream_t st, const double4 *src, dou
     }
     return;
   }
+  if (nsall && !d.packed_ahead) d.halo_pack_launches++;
   if (nsall && !d.packed_ahead)
     hipLaunchKernelGGL(k_dd_pack, dim3((nsall + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d.nsend[0], d.nsend[1],
                        d.sendlist[0], d.sendlist[1], src, d.sendbuf);

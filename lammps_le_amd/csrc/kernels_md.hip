@@ -205,7 +205,7 @@ struct ForceArgs {
   double cix, ciy, ciz, zlo_ext;
   int *cell_of, *cell_count, *cell_rank;
   // decomposed runs: border beads also write their new position into the halo send buffer (no pack launch per step)
-  const int *sendslot;
+  const int *sendslot;   // (behind its npad words: the {slot below, slot above} pairs of the beads in both lists, DeviceState::sendboth)
   double4 *send_dn, *send_up;   // the staging buffer's two halves, or the neighbours' windows (kernels_dd.hip, fast halo)
 };
 
@@ -679,6 +679,11 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     if (A.sendslot) {
       const int sl = A.sendslot[p];
       if (sl >= 0) ((sl >> 30) ? A.send_up : A.send_dn)[sl & ((1 << 30) - 1)] = ri;
+      else if (sl <= -2) {      // a slab below two ghost cutoffs: this bead is a ghost of both neighbours
+        const int *__restrict__ b = A.sendslot + A.npad + 2 * (size_t)(-2 - sl);
+        A.send_dn[b[0]] = ri;
+        A.send_up[b[1]] = ri;
+      }
     }
     if (check) {
       // Neighbor::check_distance.  Throughput shape: the float copy of the build-time positions (posf, 16 B, what the
@@ -987,7 +992,7 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
 }
 void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
   ForceArgs A = force_args(d, a.special_lj);
-  if (d.dd && p.next && d.sendslot && !d.sendslot_fallback) {
+  if (d.dd && p.next && d.sendslot) {
     A.sendslot = d.sendslot;
     if (d.fast_halo && d.direct_recv && p.which < 0) {
       // the neighbours' windows, in their sorted ghost order: what I send down arrives there "from above" and vice versa
