@@ -828,6 +828,7 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "nlocal") return e->dev ? (double)e->dev->n : 0.0;
   if (k == "nghost") return e->dev ? (double)e->dev->nghost : 0.0;
   if (k == "fene_warnings") return e->dev && e->dev->flags_h ? (double)e->dev->flags_h[FLAG_FENE_WARN] : 0.0;
+  if (k == "bond_minimg") return e->dev ? (double)e->dev->bond_minimg : 0.0;   // bonds take the per-step minimum image (1) or the frozen image words (0), as of the last run
   if (k == "host_downloads") return (double)e->host_downloads;          // whole-system downloads (Engine::download)
   if (k == "device_bytes") return e->dev ? (double)e->dev->mem.device_bytes() : 0.0;   // device blocks this handle holds
   if (k == "subset_comm_bytes") return e->subset_comm_bytes;           // this rank's share of the subset calls' collectives

@@ -29,9 +29,10 @@ def run_ranks(world, system, script, tmp_path):
     return np.load(out)
 
 
-def run_ranks_local(world, system, script, tmp_path):
+def run_ranks_local(world, system, script, tmp_path, extra=None):
     """Same as run_ranks, but the ranks are threads of this process talking through the in-process transport
-    (stream-ordered device-to-device copies): no files, no host staging, any number of ranks on the one GPU."""
+    (stream-ordered device-to-device copies): no files, no host staging, any number of ranks on the one GPU.
+    extra(lmp) -> dict: more results of a rank (every rank calls it: it may gather)."""
     import threading
     from lammps_le_amd import lammps
     from systems import write_data
@@ -62,6 +63,8 @@ def run_ranks_local(world, system, script, tmp_path):
                     res["f_" + fid] = np.array([lmp.extract_fix(fid, 0, 1, 0), lmp.extract_fix(fid, 0, 1, 1)])
                 except Exception:
                     pass
+            if extra is not None:
+                res.update(extra(lmp))
             out[rank] = res
             lmp.close()
         except Exception as e:       # a failing rank leaves the others waiting for the transport's timeout
