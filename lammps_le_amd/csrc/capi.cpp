@@ -377,7 +377,7 @@ static void scatter_subset_impl(Engine *e, const char *fn, const char *name, int
       leave++;
       if (owner != (me + 1) % W && owner != (me + W - 1) % W) far++;
     }
-    const long migcap = (long)d.npad / 4;                  // kernels_dd.hip dd_reneighbor: slots per direction
+    const long migcap = (long)d.npad / 4;                  // kernels_dd.hip rebuild_migrate: slots per direction
     fallback = e->comm->allreduce_host_max((far > 0 || leave > migcap / 2) ? 1L : 0L) != 0;
     e->subset_comm_bytes += (double)sizeof(long);
   }
@@ -389,7 +389,7 @@ static void scatter_subset_impl(Engine *e, const char *fn, const char *name, int
   }
   const int prop = dbl3 ? (k == "x" ? SUBSET_X : SUBSET_V3) : typ ? SUBSET_TYPE : (count == 3 ? SUBSET_IMG3 : SUBSET_IMG1);
   subset_scatter(d, prop, k == "f" ? 1 : 0, count, K, uid.data(), urows.data());
-  if (k == "x") d.bins_ready = false;      // bins a step kernel left behind belong to the old positions
+  if (k == "x") note_positions_replaced(d);
   if (e->host_current) apply_host();       // keep a current host copy current
 }
 
@@ -784,6 +784,7 @@ double lammps_le_stat(void *handle, const char *name) {
   std::string k = name;
   if (k == "loop_time") return e->loop_time;
   if (k == "neigh_builds") return (double)e->neigh_builds;
+  if (k == "rebuild_plan") return (double)e->rebuild_plan_bits;      // the plan the last rebuild executed: RebuildBit, rebuild_plan.h
   // time steps of the last run by the path they took: the step kernel (steps_fused_group of them its group variant), its
   // energy variant on a thermo step, the unfused kernels; the three add up to the steps of the run
   if (k == "steps_fused") return (double)e->steps_fused;

@@ -118,8 +118,6 @@ void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxsp
   d.bond_pack_stride = ((1 + bpa) + 3) & ~3;
   DEV_ALLOC(d.mem, d.bond_pack, nt * (size_t)d.bond_pack_stride);
   for (int k = 0; k < 2; k++) DEV_ALLOC(d.mem, d.bond_pack_p[k], np * (size_t)d.bond_pack_stride);
-  d.bond_pack_dirty = true;
-  d.bond_pack_p_valid = false;
   // cells of edge >= cutneigh
   d.ncells = 1;
   for (int k = 0; k < 3; k++) {
@@ -149,8 +147,7 @@ void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxsp
   d.mem.alloc_host(d.flags_h, FLAG_SEQ_SLOT + 16, "d.flags_h", hipHostMallocMapped | hipHostMallocCoherent);
   for (int k = 0; k < FLAG_SEQ_SLOT + 16; k++) d.flags_h[k] = 0;
   d.flags_seq = 0;
-  d.bins_ready = false;
-  d.cell_count_dirty = false;    // (freshly allocated arrays are zeroed)
+  note_arrays_allocated(d);      // (freshly allocated arrays are zeroed)
   HIP_CHECK(hipHostGetDevicePointer((void **)&d.flags_h_dev, d.flags_h, 0));
   // LE fix scratch
   DEV_ALLOC(d.mem, d.xt, nt);
@@ -194,7 +191,7 @@ void dev_free(DeviceState &d) {
   // words that describe freed memory
   d.rng_out = nullptr; d.gather_recv = nullptr; d.halo_flag = nullptr;
   d.rng_W = 0; d.rng_batch_raw[0] = d.rng_batch_raw[1] = 0;
-  d.bins_ready = false;
+  note_positions_replaced(d);
 }
 
 // flags reach the host through a mapped pinned page written by a one-wave kernel (a blit-copy of 64 bytes costs

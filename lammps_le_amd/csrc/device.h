@@ -270,7 +270,6 @@ struct DeviceState {
   int *gcell_start = nullptr, *gcell_count = nullptr;   // ghost ranges per cell (relative to n)
   int *sendlist[2] = {nullptr, nullptr};                // owned indices sent down / up every step
   int *sendlist_alt[2] = {nullptr, nullptr};            // ... and the buffers the next rebuild writes its reordered lists into
-  bool bpart_fresh = false;                             // the permute pass of this rebuild has written the bond-partner table
   int *gmask = nullptr;                                 // [maxtag+2] group bits by tag (bit 0 = all); only when a fix acts on a group
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
   char *angtab_dev = nullptr;                           // AngleTable in device memory (fused angle step)
@@ -380,12 +379,32 @@ void reduce_angle_partials(DeviceState &d, double *out8);
 // reductions: returns sums of `partial` columns on the host (synchronises the stream)
 void reduce_partials(DeviceState &d, double *out16);
 
-// neighbor (kernels_neigh.hip)
-void launch_reneighbor(DeviceState &d, double cutneighsq, const double special_lj[4], bool has_pair);
-// (`binned`: cell, arrival order and counts of the m_in slots are in place - the decomposed rebuild's migration pass)
-void launch_sort_owned(DeviceState &d, int m_in = -1, int n_out = -1, const int *gone = nullptr, bool binned = false);
+// neighbor (kernels_neigh.hip, kernels_dd.hip): the stages of a rebuild in the order Engine::reneighbor runs them; each
+// launches what the plan says (rebuild_plan.h).  Decomposed runs: rebuild_migrate (ownership; returns the slots to bin and
+// the beads that remain), rebuild_sort, rebuild_ghosts (borders, ghosts into cell order); one GPU: rebuild_sort alone.  Then
+// the Atom::sort emulation where it is due, then rebuild_lists.
+struct Comm;
+void rebuild_migrate(DeviceState &d, Comm &comm, const RebuildPlan &plan, int &m_in, int &n_out);
+void rebuild_sort(DeviceState &d, const RebuildPlan &plan, int m_in, int n_out, const int *gone);
+void rebuild_ghosts(DeviceState &d, Comm &comm, const RebuildPlan &plan, double cutneighsq);
+void rebuild_lists(DeviceState &d, const RebuildPlan &plan, double cutneighsq);
 void scan_cells(DeviceState &d, int *count, int *start, int nc, int total);   // start[0..nc] := exclusive scan of count[0..nc), count := 0
-void launch_lists(DeviceState &d, double cutneighsq, const double special_lj[4], bool has_pair);
+
+// The flags of DeviceState a rebuild plans from (bins_ready, cell_count_dirty, bond_pack_dirty, bond_pack_p_valid, topo_dirty,
+// map_stale) are raised from outside the rebuild through these and cleared by the rebuild's stages alone.
+inline void note_topology_changed(DeviceState &d) { d.topo_dirty = d.bond_pack_dirty = d.angle_pack_dirty = true; }   // bond / angle tables edited
+inline void note_positions_replaced(DeviceState &d) { d.bins_ready = false; }     // bins a step kernel left behind belong to the old positions
+inline void note_order_replaced(DeviceState &d) { d.bins_ready = false; d.bond_pack_p_valid = false; }   // the arrays are (about to be) refilled in another order
+inline void note_arrays_allocated(DeviceState &d) {      // dev_alloc: zeroed cell counts, no packed records yet
+  note_order_replaced(d);
+  d.cell_count_dirty = false;
+  d.bond_pack_dirty = true;
+}
+inline void note_map_allocated(DeviceState &d) { d.map_stale = true; }            // dd_alloc: map[] may hold anything
+inline void note_step_binned(DeviceState &d, bool binned) {                        // launch_step: the kernel bins (or not) what it moves
+  if (binned) d.cell_count_dirty = true;
+  d.bins_ready = binned;
+}
 
 // Atom::sort emulation (kernels_sort.hip): crank[tag] := rank in the reference's sorted local order
 void launch_atom_sort(DeviceState &d, const int nb[3], const double binv[3], bool by_tag = false);

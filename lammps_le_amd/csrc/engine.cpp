@@ -11,7 +11,6 @@
 
 namespace lmp_le {
 
-void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double sl[4], bool has_pair, bool build_lists = true);
 void dd_halo(DeviceState &d, Comm &comm);
 void dd_halo(DeviceState &d, Comm &comm, hipStream_t st, const double4 *src, double4 *dst);
 void dd_halo_wait(DeviceState &d);
@@ -159,8 +158,7 @@ void Engine::upload() {
                         "not supported by the MI355X engine (minimum-image cell lists)");
   }
   DeviceState &d = *dev;
-  d.bins_ready = false;      // the device arrays are about to be replaced (tag order): bins of the old arrays are void
-  d.bond_pack_p_valid = false;
+  note_order_replaced(d);    // the device arrays are about to be replaced (tag order)
   bool realloc = (d.ntotal != natoms || d.bpa != bpa || d.maxspecial != maxspecial || d.ntypes != ntypes || !d.pos || d.apa != apa);
   double cellcut = cutneighmax > 0.0 ? cutneighmax : std::max({box.prd[0], box.prd[1], box.prd[2]}) / 3.0;
   if (world > 1) {
@@ -467,28 +465,51 @@ static void check_device_error(Engine *e, DeviceState &d) {
   throw LammpsError(msg);
 }
 
-// defer_check: the flags of the build are published but not waited for - the caller enqueues the step kernel first
-// (it leaves the state untouched if a list overflowed) and then calls finish_reneighbor(); the host round trip of
-// the check (~25 us) is hidden behind that kernel instead of idling the GPU once per rebuild.
-void Engine::reneighbor(bool defer_check, bool sort_now) {
-  DeviceState &d = *dev;
+// What the engine knows when a rebuild starts (rebuild_plan.h): the one place the flags of DeviceState are read for it
+RebuildFacts Engine::rebuild_facts(bool can_defer, bool sort_due, bool regrow) const {
+  const DeviceState &d = *dev;
+  RebuildFacts f;
+  f.decomposed = d.dd != 0;
+  f.bins_ready = d.bins_ready; f.counts_dirty = d.cell_count_dirty; f.bonds_dirty = d.bond_pack_dirty; f.phys_valid = d.bond_pack_p_valid;
+  f.bond_minimg = d.bond_minimg != 0; f.bpa = d.bpa; f.bond_pack_stride = d.bond_pack_stride; f.bpart = d.bpart != nullptr;
   // (`pair_style zero` builds the pair list like any pair style - that is what the style is for, src/pair_zero.cpp - although
   //  no force kernel reads its pair entries: without a pair force they take the bonds from the bond-partner table)
-  // (read at every rebuild, not cached: the test that sets it shares its process with tests that must not see it)
-  const char *ovf = getenv("LAMMPS_LE_TEST_OVERFLOW_AT");
-  const long test_overflow_at = ovf ? atol(ovf) : -1;
-  if (test_overflow_at >= 0 && neigh_builds == test_overflow_at) dev_alloc_neigh(d, 4);   // test hook: force an overflow
+  f.pair = pair_lj || pair_zero;
+  for (int k = 1; k <= 3; k++) f.sf[k] = d.sflag[k];
+  f.special_asym = d.flags_h[FLAG_SPECIAL_ASYM] != 0;
+  f.row_tile = d.row_tile;
+  f.angles = angles_active();
+  f.snapshot_due = d.le_snapshot && d.topo_dirty;
+  f.map_stale = d.map_stale;
+  f.sort_due = sort_due; f.can_defer = can_defer; f.regrow = regrow;
+  f.builds = neigh_builds;
+  return f;
+}
+
+// can_defer: the caller enqueues the step kernel first (it leaves the state untouched if a list overflowed) and then calls
+// finish_reneighbor(); where the plan defers the check, the flags of the build are published but not waited for, and the host
+// round trip of the check (~25 us) is hidden behind that kernel instead of idling the GPU once per rebuild.
+void Engine::reneighbor(bool can_defer, bool sort_due) {
+  DeviceState &d = *dev;
+  const double cutneighsq = cutneighmax * cutneighmax;
+  const RebuildPlan plan = plan_rebuild(rebuild_facts(can_defer, sort_due, false), rebuild_knobs);
+  rebuild_plan_bits = plan.bits;
+  if (plan.has(RB_FORCE_OVERFLOW)) dev_alloc_neigh(d, 4);   // test hook: force an overflow
   // FLAG_MOVED / NEIGH_OVERFLOW / MAXNEIGH are zero here: they are reset by the publish kernel that reports them
   // pbc + ownership + cell order, then - on a sort step - the reference's Atom::sort (src/verlet.cpp:270-286: after pbc,
   // BEFORE neighbor->build: the pair list of this very build is stored in the new local order, which decides whose special
   // list a pair's status comes from when the lists are asymmetric), then the lists
-  if (d.dd) dd_reneighbor(d, *comm, cutneighmax * cutneighmax, special_lj, pair_lj || pair_zero, false);
-  else launch_sort_owned(d);
-  if (sort_now) emulate_atom_sort();
-  launch_lists(d, cutneighmax * cutneighmax, special_lj, pair_lj || pair_zero);
+  if (plan.decomposed) {     // collective over all ranks
+    int m_in = 0, n_out = 0;
+    rebuild_migrate(d, *comm, plan, m_in, n_out);
+    rebuild_sort(d, plan, m_in, n_out, d.gone);
+    rebuild_ghosts(d, *comm, plan, cutneighsq);
+  } else rebuild_sort(d, plan, d.n, d.n, nullptr);
+  if (plan.has(RB_ATOM_SORT)) emulate_atom_sort();
+  rebuild_lists(d, plan, cutneighsq);
   // (decomposed: the border pass of the rebuild has also checked that this rank's Langevin pools hold the draws of the beads
   //  it owns now - FLAG_RNG_MISS, kernels_dd.hip k_dd_borders)
-  if (defer_check && !d.dd) {
+  if (plan.has(RB_CHECK_DEFERRED)) {
     publish_flags(d, 1u << FLAG_MOVED);          // NEIGH_OVERFLOW stays set on the device: the step kernel reads it
     reneigh_pending = true;
   } else {
@@ -497,8 +518,8 @@ void Engine::reneighbor(bool defer_check, bool sort_now) {
     if (d.flags_h[FLAG_RNG_MISS]) { rng_late_generate(d); rng_late_count++; }
     if (d.flags_h[FLAG_NEIGH_OVERFLOW]) regrow_lists();
   }
-  if (angles_active()) launch_angle_list(d);     // NTopoAngle::build
-  if (d.le_snapshot && d.topo_dirty) {   // NTopoBond::build: the bond list the LE fixes will see until the next reneighbor
+  if (plan.has(RB_ANGLE_LIST)) launch_angle_list(d);     // NTopoAngle::build
+  if (plan.has(RB_TOPO_SNAPSHOT)) {   // NTopoBond::build: the bond list the LE fixes will see until the next reneighbor
     d.topo_dirty = false;
     launch_topo_snapshot(d);
   }
@@ -534,7 +555,9 @@ void Engine::regrow_lists() {
     dev_alloc_neigh(d, d.flags_h[FLAG_MAXNEIGH] + 16);
     HIP_CHECK(hipMemsetAsync(d.flags + FLAG_NEIGH_OVERFLOW, 0, sizeof(int), d.stream));
     HIP_CHECK(hipMemsetAsync(d.flags + FLAG_MAXNEIGH, 0, sizeof(int), d.stream));
-    launch_lists(d, cutneighmax * cutneighmax, special_lj, pair_lj || pair_zero);
+    const RebuildPlan plan = plan_rebuild(rebuild_facts(false, false, true), rebuild_knobs);
+    rebuild_plan_bits = plan.bits;
+    rebuild_lists(d, plan, cutneighmax * cutneighmax);
     sync_flags(d);
     check_device_error(this, d);
   }
@@ -952,7 +975,7 @@ void Engine::iterate(long nsteps) {
     if (decide()) {
       const bool sort_due = sortfreq > 0 && ntimestep >= nextsort;
       stamp();
-      reneighbor(plan.fused && !plan.ef && !sort_due, sort_due);     // (a whole fused step follows: the check waits behind it)
+      reneighbor(plan.fused && !plan.ef, sort_due);     // (a whole fused step follows: the check may wait behind it)
       stamp(T_NEIGH);
     } else {
       stamp();
@@ -1216,6 +1239,7 @@ void Engine::run(long nsteps) {
   const bool trace = getenv("LAMMPS_LE_TRACE_RUN") != nullptr;
   double tr0 = wall();
   init();
+  rebuild_knobs = RebuildKnobs();
   double tr1 = wall();
   // (a fix on a group that was defined since the last upload: the masks and the member ranks travel with an upload)
   if (dev && dev_current && fixes_on_groups(this) && group_sig != group_signature()) { download(); dev_current = false; }
@@ -1234,7 +1258,7 @@ void Engine::run(long nsteps) {
       else if (bondtab.style[b] != 0) all_fene = false;
     }
     const double halfmin = 0.5 * std::min({box.prd[0], box.prd[1], box.prd[2]});
-    dev->bond_minimg = (all_fene && 2.0 * r0max * 1.000001 < halfmin && !getenv("LAMMPS_LE_FREEZE_IMAGES")) ? 1 : 0;
+    dev->bond_minimg = (all_fene && 2.0 * r0max * 1.000001 < halfmin && !rebuild_knobs.freeze_images) ? 1 : 0;
   }
   dev->newton_pair = newton_pair ? 1 : 0;
   for (int k = 0; k < 3; k++) {
@@ -1248,9 +1272,7 @@ void Engine::run(long nsteps) {
   le_reneigh_step.assign(fixes.size(), -1);
   dev->le_snapshot = 0;
   for (auto &f : fixes) if (f->force_reneighbor) dev->le_snapshot = 1;
-  dev->topo_dirty = true;     // bond tables may have been edited between runs
-  dev->bond_pack_dirty = true;
-  dev->angle_pack_dirty = true;
+  note_topology_changed(*dev);     // bond tables may have been edited between runs
   beginstep = ntimestep;
   endstep = ntimestep + nsteps;
   atimestep = ntimestep;            // Integrate::init (src/integrate.cpp:48)

@@ -257,9 +257,7 @@ void FixExtrusion::post_integrate() {
   }
   ExtrusionParams p{neutral, ctcf_left, ctcf_right, ctcf_lr, btype, through_prob, groupbit};
   launch_extrusion(d, p, slot);
-  d.topo_dirty = true;
-  d.bond_pack_dirty = true;
-  d.angle_pack_dirty = true;
+  note_topology_changed(d);
   sync_flags(d);
   check_le_error(d, "extrusion");
   last_break = d.flags_h[FLAG_COUNT_A];
@@ -288,9 +286,7 @@ void FixExLoad::post_integrate() {
     }
     launch_ex_load(d, p, slot, eng->comm);
   }
-  d.topo_dirty = true;
-  d.bond_pack_dirty = true;
-  d.angle_pack_dirty = true;
+  note_topology_changed(d);
   sync_flags(d);
   check_le_error(d, style.c_str());
   last_create = d.flags_h[FLAG_COUNT_A];
@@ -312,9 +308,7 @@ void FixExUnload::post_integrate() {
   }
   ExUnloadParams p{btype, cutsq, fraction, angleflag, groupbit};
   launch_ex_unload(d, p, slot);
-  d.topo_dirty = true;
-  d.bond_pack_dirty = true;
-  d.angle_pack_dirty = true;
+  note_topology_changed(d);
   sync_flags(d);
   check_le_error(d, style.c_str());
   last_break = d.flags_h[FLAG_COUNT_A];

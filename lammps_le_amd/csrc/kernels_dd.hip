@@ -552,7 +552,7 @@ void dd_alloc(DeviceState &d, int world) {
     DEV_ALLOC(d.mem, d.sendlist[k], np); DEV_ALLOC(d.mem, d.sendlist_alt[k], np);
     DEV_ALLOC(d.mem, d.migbuf[k], np * MIG_W / 4 + 128);      // (MIG_W doubles per bead + 1024 bytes)
   }
-  d.map_stale = true;
+  note_map_allocated(d);
   DEV_ALLOC(d.mem, d.migin, np * MIG_W / 2 + 128);
   DEV_ALLOC(d.mem, d.sendbuf, np);
   DEV_ALLOC(d.mem, d.recvbuf, np);
@@ -570,8 +570,18 @@ void dd_alloc(DeviceState &d, int world) {
   (void)world;
 }
 
-// Rebuild ownership and ghosts on this rank, then sort and build lists.  Collective over all ranks.
-void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double sl[4], bool has_pair, bool build_lists) {
+// Decomposed rebuild, collective over all ranks: ownership (rebuild_migrate), then the cell sort (rebuild_sort), then
+// borders and ghosts (rebuild_ghosts).
+// counts travel rank-to-rank on the device and reach the host together with this rank's own counters: one
+// host synchronisation per phase (migration, borders) instead of three
+static void swap_counts(DeviceState &d, Comm &comm, int slot_dn, int slot_up) {
+  const int P = comm.world, me = comm.rank, dn_rank = (me + P - 1) % P, up_rank = (me + 1) % P;
+  const unsigned counters = (1u << FLAG_COUNT_A) | (1u << FLAG_COUNT_B) | (1u << FLAG_NDRAW) | (1u << FLAG_COUNT_BOTH);
+  comm.exchange(d.stream, {{d.flags + slot_dn, sizeof(int), dn_rank}, {d.flags + slot_up, sizeof(int), up_rank}},
+                {{d.flags + FLAG_RECV_UP, sizeof(int), up_rank}, {d.flags + FLAG_RECV_DN, sizeof(int), dn_rank}});
+  sync_flags(d, counters);     // published, then zeroed for the next phase
+}
+void rebuild_migrate(DeviceState &d, Comm &comm, const RebuildPlan &plan, int &m_in, int &n_out) {
   hipStream_t st = d.stream;
   dd_halo_wait(d);
   d.halo_ahead = false;
@@ -579,23 +589,14 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
   d.packed_peer = 0;       // (a halo the step kernel pushed into the neighbours' windows before a rebuild is never consumed)
   const int P = comm.world, me = comm.rank, dn_rank = (me + P - 1) % P, up_rank = (me + 1) % P;
   const double width = d.box.prd[2] / P;   // the SAME expression on every rank and in Engine::upload (owner of a bead)
-  int n = d.n, nb = std::max(1, (n + BLOCK - 1) / BLOCK);
+  const int n = d.n;
   const int migcap = (int)(((size_t)d.npad * MIG_W / 4) / MIG_W);
-  // counts travel rank-to-rank on the device and reach the host together with this rank's own counters: one
-  // host synchronisation per phase (migration, borders) instead of three
-  const unsigned counters = (1u << FLAG_COUNT_A) | (1u << FLAG_COUNT_B) | (1u << FLAG_NDRAW) | (1u << FLAG_COUNT_BOTH);
-  auto swap_counts = [&](int slot_dn, int slot_up) {
-    comm.exchange(st, {{d.flags + slot_dn, sizeof(int), dn_rank}, {d.flags + slot_up, sizeof(int), up_rank}},
-                  {{d.flags + FLAG_RECV_UP, sizeof(int), up_rank}, {d.flags + FLAG_RECV_DN, sizeof(int), dn_rank}});
-    sync_flags(d, counters);     // published, then zeroed for the next phase
-  };
   // ---- 1. migration (+ binning of what stays, + the old slots' tags out of map[]) ----
   HIP_CHECK(hipMemsetAsync(d.flags + FLAG_COUNT_A, 0, 4 * sizeof(int), st));   // COUNT_A, COUNT_B, NDRAW, NLIST
-  if (d.map_stale) {      // first rebuild on freshly uploaded arrays: map[] may hold anything
+  if (plan.has(RB_MAP_FILL))      // first rebuild on freshly uploaded arrays: map[] may hold anything
     hipLaunchKernelGGL(k_fill_int, dim3((d.maxtag + 2 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d.maxtag + 2, d.map, -1);
-    d.map_stale = false;
-  }
-  if (d.cell_count_dirty) { HIP_CHECK(hipMemsetAsync(d.cell_count, 0, ((size_t)d.ncells + 2) * sizeof(int), st)); d.cell_count_dirty = false; }
+  d.map_stale = false;
+  if (plan.has(RB_COUNT_MEMSET)) HIP_CHECK(hipMemsetAsync(d.cell_count, 0, ((size_t)d.ncells + 2) * sizeof(int), st));
   const BinArgs BA{d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0], d.cellinv[1], d.cellinv[2], d.zlo_ext, d.cell_of, d.cell_count,
                    d.tag_tmp, d.ncells};
   {
@@ -603,7 +604,7 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
     hipLaunchKernelGGL(k_dd_leave, dim3(gl), dim3(BLOCK), 0, st, n, nslots, d.npad, migcap, d.box, d.slab_lo, width, me, P, d.pos,
                        d.v[0], d.v[1], d.v[2], d.tag, d.img, d.migbuf[0], d.migbuf[1], d.gone, d.map, BA, d.flags);
   }
-  swap_counts(FLAG_COUNT_B, FLAG_NDRAW);      // what I send down arrives as the lower rank's "from above"
+  swap_counts(d, comm, FLAG_COUNT_B, FLAG_NDRAW);      // what I send down arrives as the lower rank's "from above"
   int ndn = d.flags_h[FLAG_COUNT_B], nup = d.flags_h[FLAG_NDRAW];
   int recvc[2] = {d.flags_h[FLAG_RECV_DN], d.flags_h[FLAG_RECV_UP]};   // [0] from below (their up), [1] from above
   if (ndn > migcap || nup > migcap || recvc[0] + recvc[1] > 2 * migcap)
@@ -619,15 +620,20 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
   if (narr)
     hipLaunchKernelGGL(k_dd_arrive, dim3((narr + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, narr, n, d.npad, d.migin,
                        d.pos, d.v[0], d.v[1], d.v[2], d.tag, d.img, d.gone, d.box, BA);
-  // ---- 2. cell sort of kept + arrived beads (sets map for them; the gone ones drop off the end) ----
-  launch_sort_owned(d, n + narr, n + narr - ndn - nup, d.gone, true);
-  d.n = n = n + narr - ndn - nup;
-  nb = std::max(1, (n + BLOCK - 1) / BLOCK);
+  // ---- 2. cell sort of kept + arrived beads (rebuild_sort: sets map for them; the gone ones drop off the end) ----
+  m_in = n + narr;
+  n_out = n + narr - ndn - nup;
+}
+void rebuild_ghosts(DeviceState &d, Comm &comm, const RebuildPlan &plan, double cutneighsq) {
+  hipStream_t st = d.stream;
+  const int P = comm.world, me = comm.rank, dn_rank = (me + P - 1) % P, up_rank = (me + 1) % P;
+  const double width = d.box.prd[2] / P;
+  const int n = d.n, nb = std::max(1, (n + BLOCK - 1) / BLOCK);
   // ---- 3. borders ----
   hipLaunchKernelGGL(k_dd_borders, dim3(nb), dim3(BLOCK), 0, st, n, d.pos, d.box, d.slab_lo, width,
                      std::min(sqrt(cutneighsq), d.cutghost), d.cutghost, d.bpa, d.tag, d.map, d.num_bond, d.bond_atom,
                      d.sendlist[0], d.sendlist[1], d.flags, d.phase, d.sendslot, d.sendboth, rng_validate_args(d), d.ghost_whole_shell ? 1 : 0);
-  swap_counts(FLAG_COUNT_A, FLAG_COUNT_B);
+  swap_counts(d, comm, FLAG_COUNT_A, FLAG_COUNT_B);
   d.nsend[0] = d.flags_h[FLAG_COUNT_A];
   d.nsend[1] = d.flags_h[FLAG_COUNT_B];
   d.nsend_both = d.flags_h[FLAG_COUNT_BOTH];
@@ -657,7 +663,7 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
   // ---- 4. ghosts into cell order behind the owned beads (the scan leaves the counts at zero for the next rebuild) ----
   int m = d.nghost, gb = std::max(1, (m + BLOCK - 1) / BLOCK);
   int *gcell_of = d.le_i[7], *grank = d.le_i[8], *gperm = d.le_i[9];
-  static const bool no_direct = getenv("LAMMPS_LE_NO_DIRECT_RECV") != nullptr;
+  const bool no_direct = !plan.has(RB_DIRECT_RECV);
   int *rel_out = d.le_i[10], *rel_in = d.le_i[11];
   if (m)
     hipLaunchKernelGGL(k_dd_ghost_bin, dim3(gb), dim3(BLOCK), 0, st, m, d.recvbuf, d.box, d.ncell[0], d.ncell[1],
@@ -688,8 +694,6 @@ void dd_reneighbor(DeviceState &d, Comm &comm, double cutneighsq, const double s
     }
     d.direct_recv = true;
   }
-  // ---- 5. lists (the engine builds them itself when an Atom::sort emulation has to come in between) ----
-  if (build_lists) launch_lists(d, cutneighsq, sl, has_pair);
 }
 
 // per-step forward communication of ghost positions (CommBrick::forward_comm, src/comm_brick.cpp:452-512): owned

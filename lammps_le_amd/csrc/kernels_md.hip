@@ -767,7 +767,7 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 // `groupbit` != 1: the fix acts on a group (DeviceState::gmask by tag)
 void launch_initial_integrate(DeviceState &d, const TypeTables &tt, double dtv, double triggersq, bool check, int groupbit) {
   int nb = (d.n + BLOCK - 1) / BLOCK;
-  d.bins_ready = false;     // the positions move: bins a step kernel may have left behind are stale
+  note_positions_replaced(d);     // the positions move
   hipLaunchKernelGGL(k_initial_integrate, dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.v[0], d.v[1], d.v[2],
                      d.f[0], d.f[1], d.f[2], d.xhold, tt, dtv, triggersq, check ? 1 : 0, d.flags, d.tag,
                      groupbit != 1 ? d.gmask : (const int *)nullptr, groupbit);
@@ -1011,10 +1011,9 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
   if (p.bin) {
     // the counts are zero unless an earlier launch binned and no rebuild consumed them (the scan zeroes what it reads)
     if (d.cell_count_dirty) HIP_CHECK(hipMemsetAsync(d.cell_count, 0, (size_t)(d.ncells + 1) * sizeof(int), d.stream));
-    d.cell_count_dirty = true;
     A.bin = 1;
   }
-  d.bins_ready = p.bin;
+  note_step_binned(d, p.bin);
   // LAMMPS_LE_DIAG_STEP=bits: the same kernel is launched once more BEFORE the real launch with parts switched off
   // (1 bonds, 2 pair loop, 4 draws, 8 pair gathers replaced by coalesced loads, 128 nothing); it writes only the second position buffer, which the real launch
   // overwrites, so the run is physically unchanged and a kernel trace shows what each part costs

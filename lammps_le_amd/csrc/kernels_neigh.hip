@@ -639,129 +639,143 @@ __global__ __launch_bounds__(BLOCK, BUILD_WAVES_PER_SIMD) void k_build_neigh_dia
   build_body<NOSPECIAL, ASYM, FRAC>(n, npad, maxneigh, pos, posf, cutf, bandf, tag, map, cell_start, gcell_start, dd, zlo_ext, ncx, ncy, ncz, cix, ciy, ciz, box, cutneighsq, margin, nspecial, special, ms, sf1, sf2, sf3, bondtab, bpa, bshift, neigh, numneigh, flags, diag, PairOrder{});
 }
 
-// phase 1: wrap owned beads, sort them into cell order (ties by ID), permute the physical arrays.
-// Decomposed runs pass m_in = slots to bin (kept + gone + arrived) and `gone`; n_out beads remain afterwards.
-static void ensure_bond_pack(DeviceState &d) {
-  if (!d.bond_pack_dirty) return;
-  hipLaunchKernelGGL(k_bond_pack, dim3((d.maxtag + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, d.stream, d.maxtag, d.bpa, d.bond_pack_stride,
-                     d.num_bond, d.bond_type, d.bond_atom, d.bond_pack);
-  d.bond_pack_dirty = false;
-  d.bond_pack_p_valid = false;
+// The build dispatcher: the instantiation a plan names, handed to f(kernel, std::bool_constant<asym>); false: there is none
+// (tests/test_rebuild_plan_cpu.py holds plan_rebuild against it through lammps_le_test_rebuild_plan)
+static_assert(BPART_EXCL_MAX == SPMAX, "plan_rebuild takes the exclusions from the bond-partner table for as many partners as the build keeps in registers");
+template <class F> static bool with_build_kernel(const RebuildPlan &p, F &&f) {
+  bool found = false;
+  with_flags([&](auto NOSP, auto AS, auto FR) {
+    if constexpr (AS && !NOSP) { f(k_build_neigh_asym<FR>, AS); found = true; }
+    else if constexpr (!AS && !(NOSP && FR)) { f(k_build_neigh<NOSP, false, FR>, AS); found = true; }
+  }, p.has(RB_NOSP), p.has(RB_ASYM), p.has(RB_FRAC));
+  return found;
 }
+
 void scan_cells(DeviceState &d, int *count, int *start, int nc, int total) {
   const int sb = (nc + SCAN_BLOCK - 1) / SCAN_BLOCK;
   hipLaunchKernelGGL(k_scan_local, dim3(sb), dim3(SCAN_BLOCK), 0, d.stream, nc, count, start, d.scan_tmp);
   hipLaunchKernelGGL(k_scan_add, dim3(sb), dim3(SCAN_BLOCK), 0, d.stream, nc, start, d.scan_tmp, total);
 }
-void launch_sort_owned(DeviceState &d, int m_in, int n_out, const int *gone, bool binned) {
-  if (m_in < 0) m_in = n_out = d.n;
+static void bond_pack(DeviceState &d) {
+  hipLaunchKernelGGL(k_bond_pack, dim3((d.maxtag + 1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, d.stream, d.maxtag, d.bpa, d.bond_pack_stride,
+                     d.num_bond, d.bond_type, d.bond_atom, d.bond_pack);
+  d.bond_pack_dirty = false;
+}
+// sort stage: wrap the owned beads, sort them into cell order (ties by ID), permute the physical arrays.
+// Decomposed runs pass m_in = slots to bin (kept + gone + arrived; their cell, arrival order and counts are in place - the
+// migration stage) and `gone`; n_out beads remain afterwards.
+void rebuild_sort(DeviceState &d, const RebuildPlan &plan, int m_in, int n_out, const int *gone) {
   int nb = std::max(1, (m_in + BLOCK - 1) / BLOCK);
   const int nc = d.ncells + (gone ? 1 : 0);     // + sentinel cell
   hipStream_t st = d.stream;
   // the step kernel that produced these positions may already have binned them (cell_of, arrival ranks, counts): then
   // only Domain::pbc is left, and k_permute applies it while it moves the beads
-  const bool prebinned = d.bins_ready && !gone && !d.dd && m_in == d.n;
-  d.bins_ready = false;
-  if (!prebinned && !binned) {
-    if (d.cell_count_dirty) HIP_CHECK(hipMemsetAsync(d.cell_count, 0, (size_t)(nc + 1) * sizeof(int), st));   // bins nobody consumed
+  if (plan.has(RB_COUNT_MEMSET) && !plan.decomposed) HIP_CHECK(hipMemsetAsync(d.cell_count, 0, (size_t)(nc + 1) * sizeof(int), st));   // bins nobody consumed
+  if (plan.has(RB_WRAP_BIN))
     hipLaunchKernelGGL(k_wrap_bin, dim3(nb), dim3(BLOCK), 0, st, m_in, d.pos, d.img, d.npad, d.box, d.ncell[0],
                        d.ncell[1], d.ncell[2], d.cellinv[0], d.cellinv[1], d.cellinv[2], d.zlo_ext, d.cell_of,
                        d.cell_count, d.tag_tmp, d.flags, gone, d.ncells, d.row_tile);
-  }
   scan_cells(d, d.cell_count, d.cell_start, nc, m_in);
+  d.bins_ready = false;
   d.cell_count_dirty = false;      // k_scan_local left the counts at zero
   hipLaunchKernelGGL(k_scatter, dim3(nb), dim3(BLOCK), 0, st, m_in, d.cell_of, d.cell_start, d.tag_tmp, d.perm);
   // one GPU, bonds that need no frozen image: the permute pass also writes the bond-partner table (see k_permute)
-  static const bool no_fuse = getenv("LAMMPS_LE_NO_PERMUTE_BONDS") != nullptr;
-  const bool with_bonds = !d.dd && !gone && d.bond_minimg && d.bpa > 0 && d.bpart && !no_fuse;
-  if (with_bonds) ensure_bond_pack(d);
-  static const bool no_phys = getenv("LAMMPS_LE_NO_PHYS_BOND_PACK") != nullptr;
-  const bool phys = with_bonds && d.bond_pack_stride == 4 && !no_phys;
-  if (phys && !d.bond_pack_p_valid) {
+  const bool with_bonds = plan.has(RB_PERMUTE_BONDS), phys = plan.has(RB_PERMUTE_PHYS);
+  if (with_bonds && plan.has(RB_BOND_PACK)) bond_pack(d);
+  if (plan.has(RB_BOND_PACK_PHYS)) {
     const int words = m_in * d.bond_pack_stride;
     hipLaunchKernelGGL(k_bond_pack_phys, dim3((words + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, m_in, d.bond_pack_stride, d.tag, d.bond_pack,
                        d.bond_pack_p[0]);
   }
   d.bond_pack_p_valid = phys;
   hipLaunchKernelGGL(k_sort_cells, dim3((d.ncells + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, d.ncells,
-                     d.cell_start, d.perm, d.tag, with_bonds ? d.map : (int *)nullptr);
+                     d.cell_start, d.perm, d.tag, plan.has(RB_SORT_WRITES_MAP) ? d.map : (int *)nullptr);
   const int n = n_out;
   nb = std::max(1, (n + BLOCK - 1) / BLOCK);
   BondTabArgs BT{d.bpa, d.maxtag, d.num_bond, d.bond_type, d.bond_atom, d.bond_pack, d.bond_pack_stride, with_bonds ? d.bpart : (int *)nullptr,
                  nullptr, nullptr, nullptr, 0.0, 0.0, 0.0};
   hipLaunchKernelGGL(k_permute, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.perm, d.pos, d.pos_tmp, d.xhold, d.v[0],
                      d.v[1], d.v[2], d.v_tmp[0], d.v_tmp[1], d.v_tmp[2], d.tag, d.tag_tmp, d.img, d.img_tmp, d.map, d.posf,
-                     prebinned ? 1 : 0, d.box, BT, phys ? (const int4 *)d.bond_pack_p[0] : (const int4 *)nullptr, (int4 *)d.bond_pack_p[1], d.flags);
+                     plan.has(RB_PREBINNED) ? 1 : 0, d.box, BT, phys ? (const int4 *)d.bond_pack_p[0] : (const int4 *)nullptr, (int4 *)d.bond_pack_p[1], d.flags);
   if (phys) std::swap(d.bond_pack_p[0], d.bond_pack_p[1]);
-  d.bpart_fresh = with_bonds;
   std::swap(d.pos, d.pos_tmp);
   for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]);
   std::swap(d.tag, d.tag_tmp);
   std::swap(d.img, d.img_tmp);
+  d.n = n_out;
 }
 
-// phase 2: bond-partner table + full neighbor list of the owned beads (ghosts, if any, already in place)
-void launch_lists(DeviceState &d, double cutneighsq, const double sl[4], bool has_pair) {
+// lists stage: bond-partner table + full neighbor list of the owned beads (ghosts, if any, already in place)
+void rebuild_lists(DeviceState &d, const RebuildPlan &plan, double cutneighsq) {
   int n = d.n, nb = (n + BLOCK - 1) / BLOCK;
   if (nb == 0) nb = 1;
   hipStream_t st = d.stream;
-  ensure_bond_pack(d);
-  BondTabArgs BT{d.bpa, d.maxtag, d.num_bond, d.bond_type, d.bond_atom, d.bond_pack, d.bond_pack_stride, d.bpart, d.dd ? d.phase : nullptr,
-                 d.pos, d.bond_minimg ? nullptr : d.bshift, d.box.half[0], d.box.half[1], d.box.half[2]};
+  const bool freeze = plan.has(RB_FROZEN_IMAGES);
+  if (plan.has(RB_BOND_PACK) && !plan.has(RB_PERMUTE_BONDS)) bond_pack(d);
+  BondTabArgs BT{d.bpa, d.maxtag, d.num_bond, d.bond_type, d.bond_atom, d.bond_pack, d.bond_pack_stride, d.bpart, plan.decomposed ? d.phase : nullptr,
+                 d.pos, freeze ? d.bshift : nullptr, d.box.half[0], d.box.half[1], d.box.half[2]};
   // (a launch of its own: folded into the prologue of the list build it made that kernel 48 us slower to save 16, and
   // even the unused extra kernel argument cost the build 32 us)
-  if (!d.bpart_fresh) hipLaunchKernelGGL(k_bond_table, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.tag, d.map, BT, d.flags);
-  d.bpart_fresh = false;      // (a second call for the same order - the list table grew - re-derives the same table)
-  if (has_pair) {
-    const int sf1 = d.sflag[1], sf2 = d.sflag[2], sf3 = d.sflag[3];
-    const int ddcode = d.dd ? 1 : (d.row_tile ? 0 : 2);     // see build_body   // Engine::special_flag (lj AND coul weights)
-    double margin = sqrt(cutneighsq) * (1.0 + 1e-12);
-    // FP32 test: a float coordinate is off by <= M * 2^-24 (M = largest |coordinate|), a separation component
-    // (difference, periodic shift with a float box length) by e_d <= 8 * M * 2^-24, the squared distance of a pair
-    // near the cutoff by <= 2 * sqrt(3) * r * e_d + rounding; pairs beyond 1.5 * cutneigh are far outside any band
-    double cn = sqrt(cutneighsq), M = 0.0;
-    for (int k = 0; k < 3; k++) M = std::max({M, fabs(d.box.lo[k]), fabs(d.box.hi[k])});
-    double e_d = 8.0 * M * 5.97e-8;
-    float cutf = (float)cutneighsq;
-    float bandf = (float)(4.0 * 1.5 * cn * e_d + 3.0 * e_d * e_d + 1e-5 * cutneighsq);
-    if (getenv("LAMMPS_LE_BUILD_FP64")) bandf = 1e30f;     // diagnostic: every candidate takes the FP64 test
-    const bool frac = sf1 == 2 || sf2 == 2 || sf3 == 2;      // some special weight is neither 0 nor 1
-    // exclusions = bond partners (`special_bonds fene`-like flags, symmetric lists): read from the bond-partner table
-    const bool from_bpart = sf1 == 0 && sf2 == 1 && sf3 == 1 && d.bpa >= 1 && d.bpa <= SPMAX &&
-                            !d.flags_h[FLAG_SPECIAL_ASYM] && !getenv("LAMMPS_LE_NO_BPART_EXCL");
-    const int *nsp = from_bpart ? (const int *)nullptr : d.nspecial;
-    const int *spl = from_bpart ? (const int *)d.bpart : d.special;
-    const int msp = from_bpart ? d.bpa : d.maxspecial;
-    // one argument list for the list builds: symmetric special lists (NOSP: no special list at all), the build that follows
-    // the reference's pair order (sticky flag, read back at the last sync; `last` is its PairOrder) and the diagnostic one
-    auto build = [&](auto kernel, const int *nsp, const int *spl, int msp, int *counts, int *flags, auto last) {
-      hipLaunchKernelGGL(kernel, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.maxneigh, d.pos, d.posf, cutf, bandf, d.tag, d.map,
-                         d.cell_start, d.gcell_start, ddcode, d.zlo_ext, d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0],
-                         d.cellinv[1], d.cellinv[2], d.box, cutneighsq, margin, nsp, spl, msp, sf1,
-                         sf2, sf3, d.bpart, d.bpa, d.bond_minimg ? nullptr : d.bshift, d.neigh, counts, flags, last);
-    };
-    const bool nosp = sf1 == 1 && sf2 == 1 && sf3 == 1, asym = !nosp && d.flags_h[FLAG_SPECIAL_ASYM];
-    PairOrder O{};
-    if (asym) {
-      O.crank = d.ident_order ? (const int *)nullptr : d.crank;
-      O.newton = d.newton_pair;
-      for (int k = 0; k < 3; k++) {
-        O.lo[k] = d.box.lo[k]; O.hi[k] = d.box.hi[k]; O.prd[k] = d.box.prd[k]; O.half[k] = d.box.half[k];
-        O.bininv[k] = d.ref_bininv[k]; O.nbin[k] = d.ref_nbin[k];
-      }
+  if (plan.has(RB_BOND_TABLE)) hipLaunchKernelGGL(k_bond_table, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.tag, d.map, BT, d.flags);
+  if (!plan.has(RB_BUILD)) return;
+  const int sf1 = d.sflag[1], sf2 = d.sflag[2], sf3 = d.sflag[3];     // Engine::special_flag (lj AND coul weights)
+  const int ddcode = plan.ddcode();     // see build_body
+  double margin = sqrt(cutneighsq) * (1.0 + 1e-12);
+  // FP32 test: a float coordinate is off by <= M * 2^-24 (M = largest |coordinate|), a separation component
+  // (difference, periodic shift with a float box length) by e_d <= 8 * M * 2^-24, the squared distance of a pair
+  // near the cutoff by <= 2 * sqrt(3) * r * e_d + rounding; pairs beyond 1.5 * cutneigh are far outside any band
+  double cn = sqrt(cutneighsq), M = 0.0;
+  for (int k = 0; k < 3; k++) M = std::max({M, fabs(d.box.lo[k]), fabs(d.box.hi[k])});
+  double e_d = 8.0 * M * 5.97e-8;
+  float cutf = (float)cutneighsq;
+  float bandf = (float)(4.0 * 1.5 * cn * e_d + 3.0 * e_d * e_d + 1e-5 * cutneighsq);
+  if (plan.has(RB_FP64)) bandf = 1e30f;     // diagnostic: every candidate takes the FP64 test
+  // exclusions = bond partners (`special_bonds fene`-like flags, symmetric lists): read from the bond-partner table
+  const bool from_bpart = plan.has(RB_EXCL_BPART);
+  const int *nsp = from_bpart ? (const int *)nullptr : d.nspecial;
+  const int *spl = from_bpart ? (const int *)d.bpart : d.special;
+  const int msp = from_bpart ? d.bpa : d.maxspecial;
+  // one argument list for the list builds: symmetric special lists (NOSP: no special list at all), the build that follows
+  // the reference's pair order (`last` is its PairOrder) and the diagnostic one
+  auto build = [&](auto kernel, const int *nsp, const int *spl, int msp, int *counts, int *flags, auto last) {
+    hipLaunchKernelGGL(kernel, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.maxneigh, d.pos, d.posf, cutf, bandf, d.tag, d.map,
+                       d.cell_start, d.gcell_start, ddcode, d.zlo_ext, d.ncell[0], d.ncell[1], d.ncell[2], d.cellinv[0],
+                       d.cellinv[1], d.cellinv[2], d.box, cutneighsq, margin, nsp, spl, msp, sf1,
+                       sf2, sf3, d.bpart, d.bpa, freeze ? d.bshift : nullptr, d.neigh, counts, flags, last);
+  };
+  PairOrder O{};
+  if (plan.has(RB_ASYM)) {
+    O.crank = d.ident_order ? (const int *)nullptr : d.crank;
+    O.newton = d.newton_pair;
+    for (int k = 0; k < 3; k++) {
+      O.lo[k] = d.box.lo[k]; O.hi[k] = d.box.hi[k]; O.prd[k] = d.box.prd[k]; O.half[k] = d.box.half[k];
+      O.bininv[k] = d.ref_bininv[k]; O.nbin[k] = d.ref_nbin[k];
     }
-    with_flags([&](auto NOSP, auto AS, auto FR) {
-      if constexpr (AS && !NOSP) build(k_build_neigh_asym<FR>, nsp, spl, msp, d.numneigh, d.flags, O);
-      else if constexpr (!AS && !(NOSP && FR)) build(k_build_neigh<NOSP, false, FR>, nsp, spl, msp, d.numneigh, d.flags, 0);
-    }, nosp, asym, frac && !nosp);
-    if (const char *dg = getenv("LAMMPS_LE_DIAG_BUILD"))     // diagnostics: extra launch, entry stores off, scratch counters
-      build(k_build_neigh_diag<false, false, false>, d.nspecial, d.special, d.maxspecial, d.cell_of, d.flags + FLAG_AUX - FLAG_MAXNEIGH, atoi(dg) | 1);
   }
+  const bool known = with_build_kernel(plan, [&](auto kernel, auto AS) {
+    if constexpr (AS) build(kernel, nsp, spl, msp, d.numneigh, d.flags, O);
+    else build(kernel, nsp, spl, msp, d.numneigh, d.flags, 0);
+  });
+  if (!known) throw LammpsError("internal: the rebuild plan names a list build that does not exist");
+  if (plan.has(RB_DIAG_BUILD))     // diagnostics: extra launch, entry stores off, scratch counters
+    build(k_build_neigh_diag<false, false, false>, d.nspecial, d.special, d.maxspecial, d.cell_of, d.flags + FLAG_AUX - FLAG_MAXNEIGH, plan.diag_bits);
 }
 
-void launch_reneighbor(DeviceState &d, double cutneighsq, const double sl[4], bool has_pair) {
-  launch_sort_owned(d);
-  launch_lists(d, cutneighsq, sl, has_pair);
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): the plan for the facts under the
+// environment switches as they stand at this call.  facts = decomposed, bins_ready, counts_dirty, bonds_dirty, phys_valid,
+// bond_minimg, bpa, bond_pack_stride, bpart, pair, sf1, sf2, sf3, special_asym, row_tile, angles, snapshot_due, map_stale,
+// sort_due, can_defer, regrow, builds; out = the plan's bits, diag_bits, and whether the build dispatcher holds the
+// instantiation the plan names (its own look-up, nothing is launched; 0 for a plan without a build)
+extern "C" void lammps_le_test_rebuild_plan(const int *facts, int *out) {
+  RebuildFacts f;
+  f.decomposed = facts[0]; f.bins_ready = facts[1]; f.counts_dirty = facts[2]; f.bonds_dirty = facts[3]; f.phys_valid = facts[4];
+  f.bond_minimg = facts[5]; f.bpa = facts[6]; f.bond_pack_stride = facts[7]; f.bpart = facts[8]; f.pair = facts[9];
+  f.sf[1] = facts[10]; f.sf[2] = facts[11]; f.sf[3] = facts[12]; f.special_asym = facts[13]; f.row_tile = facts[14];
+  f.angles = facts[15]; f.snapshot_due = facts[16]; f.map_stale = facts[17]; f.sort_due = facts[18]; f.can_defer = facts[19];
+  f.regrow = facts[20]; f.builds = facts[21];
+  const RebuildPlan p = plan_rebuild(f, RebuildKnobs());
+  out[0] = (int)p.bits; out[1] = p.diag_bits;
+  out[2] = p.has(RB_BUILD) && with_build_kernel(p, [](auto, auto) {});
 }
 
 }  // namespace lmp_le

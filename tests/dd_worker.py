@@ -42,7 +42,7 @@ res = dict(x=lmp.gather("x"), v=lmp.gather("v"), image=lmp.gather("image"), type
            nspecial=lmp.gather("nspecial"), special=lmp.gather("special"),
            thermo=np.array([lmp.get_thermo(k) for k in ("temp", "epair", "emol", "etotal", "press", "bonds")]),
            neigh_pairs=np.array([lmp.stat("neigh_pairs")]), builds=np.array([lmp.stat("neigh_builds")]),
-           window_exchanges=np.array([lmp.stat("halo_window_exchanges")]),
+           window_exchanges=np.array([lmp.stat("halo_window_exchanges")]), rebuild_plan=np.array([lmp.stat("rebuild_plan")]),
            window_mismatches=np.array([lmp.stat("halo_window_mismatches")]))
 for fid in ("loop", "loading", "unloading"):
     try:

@@ -29,7 +29,7 @@ def delta(box, cutneigh):
 
 
 def fp32_band(box, cutneigh):
-    """The FP32 error band of the list build, restated from kernels_neigh.hip launch_lists (`bandf`).  If that formula is
+    """The FP32 error band of the list build, restated from kernels_neigh.hip rebuild_lists (`bandf`).  If that formula is
     ever narrowed, the cutoff ladder of neigh_inputs.py has to be derived again from the new one."""
     box = np.asarray(box, dtype=np.float64)
     M = float(np.abs(box).max())

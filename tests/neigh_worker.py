@@ -49,6 +49,7 @@ def main():
     lmp = lammps(cmdargs=["-screen", "none"])
     if world > 1:
         lmp.comm_init("shm", rank, world, session=session)
+    plans = []
     for ln in open(scriptfile).read().split("\n"):
         w = ln.split("#")[0].split()
         if w and w[0] == "read_data":
@@ -56,11 +57,14 @@ def main():
             write_data(path, system)
             ln = "read_data " + path
         lmp.command(ln)
+        if w and w[0] == "run":
+            plans.append(lmp.stat("rebuild_plan"))          # the plan of the last rebuild of every run command
     res = fetch_list(lmp)
     # (gathers and the pair count are collective: every rank calls them)
     res.update(x=lmp.gather("x"), image=lmp.gather("image"), num_bond=lmp.gather("num_bond"), bond_type=lmp.gather("bond_type"), bond_atom=lmp.gather("bond_atom"),
                neigh_pairs=np.array([lmp.stat("neigh_pairs")]), builds=np.array([lmp.stat("neigh_builds")]),
-               maxneigh=np.array([lmp.stat("maxneigh")]))
+               maxneigh=np.array([lmp.stat("maxneigh")]), rebuild_plan=np.array(plans, dtype=np.int64),
+               bond_minimg=np.array([lmp.stat("bond_minimg")]))
     np.savez("%s.r%d.npz" % (out, rank), **res)
     lmp.close()
 

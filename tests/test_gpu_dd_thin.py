@@ -365,8 +365,8 @@ def test_fixes_on_a_group_on_thin_slabs(tmp_path):
 
 
 def test_md_on_thin_slabs_without_direct_receive(tmp_path, monkeypatch):
-    """LAMMPS_LE_NO_DIRECT_RECV=1 (latched per process, hence one process per rank): the halo lands in the receive buffer and
-    an unpack kernel scatters it; the send lists keep the order k_dd_borders gave them."""
+    """LAMMPS_LE_NO_DIRECT_RECV=1 (read at every run command; one process per rank all the same): the halo lands in the receive
+    buffer and an unpack kernel scatters it; the send lists keep the order k_dd_borders gave them."""
     monkeypatch.setenv("LAMMPS_LE_NO_DIRECT_RECV", "1")
     monkeypatch.setenv("LAMMPS_LE_OVERLAP", "0")
     monkeypatch.setenv("LAMMPS_LE_FAST_HALO_VERIFY", "0")
@@ -377,6 +377,9 @@ def test_md_on_thin_slabs_without_direct_receive(tmp_path, monkeypatch):
     r = run_ranks(4, s, script, tmp_path)
     assert_md(r, o)
     assert int(r["window_exchanges"][0]) == 0          # (the windows need the receiver's sorted order)
+    import rebuild_rules as R
+    plan = int(r["rebuild_plan"][0])                   # the last rebuild: decomposed, no reorder of the send lists
+    assert not plan & R.DIRECT_RECV and (plan & R.DDCODE) >> R.DDCODE_SHIFT == 1 and not plan & (R.PREBINNED | R.WRAP_BIN)
 
 
 # ---- 8: still refused ---------------------------------------------------------------------------------------------------

@@ -8,7 +8,9 @@ lammps_le_test_neighbor_list (tags, decoded special bits, the positions the list
      UNDECIDED (asserted here on those positions, and for every input without a GPU in test_neigh_reference_cpu.py);
  (c) that the bond entries that open each bead's list are the bonds the bead stores, as a multiset of (type, partner) -
      both ends of a bond carry it (k_bond_table reads the per-atom bond tables, which hold every bond on both atoms);
- (d) that stat("neigh_pairs") counts the entries the hook returned.
+ (d) that stat("neigh_pairs") counts the entries the hook returned;
+ (e) where the case is about the path a rebuild takes, that stat("rebuild_plan") - the plan the last rebuild executed - is
+     what the test hook lammps_le_test_rebuild_plan answers for the facts the case is meant to produce (rebuild_rules.py).
 
 Out of scope: runs whose special lists have become asymmetric (k_build_neigh_asym: the expected code there depends on the
 reference's half-list storage order; covered through forces by the LE fuzz suites), and angles."""
@@ -24,6 +26,7 @@ import pytest
 
 import neigh_inputs as I
 import neigh_reference as R
+import rebuild_rules as P
 from neigh_worker import fetch_list
 from systems import CHAIN_SCRIPT, run_oracle, run_product, wrap_into_box
 
@@ -67,6 +70,28 @@ def check_list(L, system, topo, neigh_pairs, weights=FENE, x_now=None):
     assert rep.ok, str(rep)
     assert neigh_pairs == len(L["itag"])
     return x, ref
+
+
+def planned(topo, n, weights=FENE, minimg=1, **facts):
+    """(e): the hook's plan for a run of the chain scripts on `topo` (the gathered bond tables of n beads: their width is the
+    bonds per atom) under special weights `weights`; `facts` name what differs from the setup build of a handle's first run
+    on one GPU (bond records to pack, nothing binned, no physical records yet)."""
+    bpa = np.asarray(topo[1]).size // n
+    lj, coul = weights
+    sf = [0 if (a, b) == (0.0, 0.0) else 1 if a == 1.0 else 2 for a, b in zip(lj, coul)]          # Engine::special_flag
+    f = dict(bonds_dirty=1, bond_minimg=int(minimg), bpa=bpa, bond_pack_stride=(1 + bpa + 3) & ~3, sf1=sf[0], sf2=sf[1], sf3=sf[2])
+    f.update(facts)
+    bits, _, known = P.hook()(P.facts(**f))
+    assert known == 1 and bits == P.expected(P.facts(**f), {k: os.environ[k] for k in P.SWITCHES if k in os.environ})[0]
+    return bits
+
+
+def last_rebuild(script, system, builds, steps):
+    """Facts of the last rebuild inside a run of `steps` steps that rebuilt `builds` times: the packed records are current,
+    and the check is deferred behind the next step kernel unless the rebuild fell on the run's last step, which is a thermo
+    step (the oracle tells: one step fewer, one build fewer)."""
+    on_last_step = run_oracle(script.replace("run %d" % steps, "run %d" % (steps - 1)), system).neigh_builds() != builds
+    return dict(bonds_dirty=0, can_defer=int(not on_last_step), builds=int(builds) - 1)
 
 
 def run_and_check(system, script, tmp_path, weights=FENE, current=True):
@@ -127,7 +152,7 @@ def test_cutoff_ladder(tmp_path, origin, monkeypatch):
         a = nchain + m["row"] + 1
         assert ((a, a + 1) in listed) == (m["side"] < 0) and ((a + 1, a) in listed) == (m["side"] < 0), m
     lmp.close()
-    monkeypatch.setenv("LAMMPS_LE_BUILD_FP64", "1")          # read at every launch of the build
+    monkeypatch.setenv("LAMMPS_LE_BUILD_FP64", "1")          # read at every run command
     lmp64 = run_product(I.ZERO_SCRIPT + "run 0\n", s, tmp_path)
     L64 = fetch_list(lmp64)
     for k in ("owned", "itag", "jtag", "code", "btag", "bjtag", "btype"):
@@ -144,6 +169,11 @@ def test_dense_cluster_regrows_the_table(tmp_path):
     assert lmp.stat("maxneigh") > I.initial_maxneigh(n, s["box"])
     per_bead = np.bincount(L["itag"], minlength=n + 1)
     assert (per_bead[n + 1 - I.CLUSTER_BEADS:] >= I.CLUSTER_BEADS - 1).all() and per_bead.max() <= lmp.stat("maxneigh")
+    # (e) the last plan executed is the regrow pass: the bond table and the build, nothing else
+    topo = (lmp.gather("num_bond"), lmp.gather("bond_type"), lmp.gather("bond_atom"))
+    plan = int(lmp.stat("rebuild_plan"))
+    assert plan == planned(topo, n, FENE, lmp.stat("bond_minimg"), regrow=1, bonds_dirty=0, phys_valid=1)
+    assert plan & P.LAUNCHES == P.BOND_TABLE | P.BUILD
     lmp.close()
 
 
@@ -171,6 +201,14 @@ def test_special_codes(tmp_path, case):
         assert codes[1] > 1000 and codes[2] == 0 and codes[3] == 0
     else:
         assert codes[1] == codes[2] == codes[3] == 0
+    # (e) where the exclusions come from and which build stores them: as the weights and the bonds per atom say
+    topo = (lmp.gather("num_bond"), lmp.gather("bond_type"), lmp.gather("bond_atom"))
+    plan = int(lmp.stat("rebuild_plan"))
+    assert plan == planned(topo, len(x), (lj, coul), lmp.stat("bond_minimg"))
+    bpa = np.asarray(topo[1]).size // len(x)
+    assert bool(plan & P.EXCL_BPART) == (args == "fene" and bpa <= 4) and (bpa <= 4) == (not hub)
+    assert bool(plan & P.NOSP) == (case == "lj-1-1-1") and not plan & P.ASYM
+    assert bool(plan & P.FRAC) == (case in ("lj-fractional", "lj-0-1-1-coul-1-1-1"))
     lmp.close()
 
 
@@ -185,10 +223,15 @@ def test_interior_and_almost_interior_wavefronts(tmp_path):
 
 
 # ---- 8: rebuilds inside a run --------------------------------------------------------------------------------------------
-# the step kernel picks its shape by system size, from switches read once per process: small systems (these) run four lanes
+# the step kernel picks its shape by system size, from switches read at every run command: small systems (these) run four lanes
 # per bead with loads issued ahead; the shape of the large ones tests the displacement against the FLOAT copy of the build
 # positions inside `hold_band` and bins the new positions itself, so that the next rebuild skips k_wrap_bin
 SHAPES = {"small-system-shape": {}, "throughput-shape": {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "0"}}
+# the chain has no bond of type 2: with that type's R0 at 1.5 instead of 4.0 every 2 R0 is below half the 6.3-wide box of
+# rebuild_chain, the per-step minimum image is provably the frozen one (stat "bond_minimg" 1) and the permute pass writes
+# the bond-partner table - the path of the benchmark systems
+MINIMG_SCRIPT = CHAIN_SCRIPT.replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 30.0 1.5 1.0 1.0")
+assert MINIMG_SCRIPT != CHAIN_SCRIPT
 
 
 @pytest.mark.parametrize("shape", sorted(SHAPES))
@@ -199,13 +242,22 @@ def test_rebuilds_inside_a_run(tmp_path, shape):
     coordinate magnitude M / 16.9 (every rounding seed scales with the ulp of a coordinate, the chaotic growth does not).
     Measured on an MI355X, both shapes: 7 builds, max |x - x_oracle| 2.7e-12 (bound 2.4e-7)."""
     s = I.rebuild_chain()
-    script = CHAIN_SCRIPT + "fix 1 all nve\nfix 2 all langevin 1.0 1.0 1.0 904297\nrun 60\n"
+    script = MINIMG_SCRIPT + "fix 1 all nve\nfix 2 all langevin 1.0 1.0 1.0 904297\nrun 60\n"
     (r,) = run_in_children(1, s, script, tmp_path, env=SHAPES[shape])
     x, ref = check_list(r, s, (r["num_bond"], r["bond_type"], r["bond_atom"]), r["neigh_pairs"][0])
     builds = r["builds"][0]
     assert builds >= 3
     o = run_oracle(script, s)
     assert builds == o.neigh_builds()
+    # (e) the last rebuild: fed by the step kernel's bins in the throughput shape, by k_wrap_bin in the other; the permute
+    # writes the bond table from the physical records either way
+    binned = int(shape == "throughput-shape")
+    plan = int(r["rebuild_plan"][-1])
+    assert r["bond_minimg"][0] == 1
+    assert plan == planned((r["num_bond"], r["bond_type"], r["bond_atom"]), len(x), bins_ready=binned, counts_dirty=binned, phys_valid=1,
+                           **last_rebuild(script, s, builds, 60))
+    assert bool(plan & P.PREBINNED) == binned and bool(plan & P.WRAP_BIN) == (not binned)
+    assert plan & P.PERMUTE_BONDS and plan & P.PERMUTE_PHYS and not plan & (P.BOND_TABLE | P.BOND_PACK_PHYS)
     box = np.asarray(s["box"])
     prd = box[:, 1] - box[:, 0]
     dev = np.abs((r["x"] + r["image"] * prd) - (o.x() + o.image() * prd)).max()
@@ -213,6 +265,46 @@ def test_rebuilds_inside_a_run(tmp_path, shape):
     print("neigh_builds %d, max |x - x_oracle| %.3e (bound %.3e)" % (builds, dev, 1e-9 * max(1.0, M / 16.9)))
     assert dev <= 1e-9 * max(1.0, M / 16.9)
     assert np.abs(r["x"] - x).max() > 1e-3          # (the list is the last build's, not the current positions')
+
+
+# ---- 8a: the bond table by its other paths --------------------------------------------------------------------------------
+# frozen images (a bond style that is not fene; fene with LAMMPS_LE_FREEZE_IMAGES=1): k_bond_table writes the table and the
+# image words, the permute moves beads only.  A hub of six bonds: records of two int4, the permute writes the table from the
+# records by tag (bond type 2 with R0 3.5: 2 R0 stays below half the 15.8-wide box, the minimum image holds).
+HARMONIC = CHAIN_SCRIPT.replace("bond_style fene", "bond_style harmonic").replace("bond_coeff 1 30.0 1.5 1.0 1.0", "bond_coeff 1 30.0 1.05") \
+    .replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 30.0 1.05")
+BOND_PATHS = {"harmonic": (HARMONIC, {}), "fene-frozen": (MINIMG_SCRIPT, {"LAMMPS_LE_FREEZE_IMAGES": "1"}),
+              "fene-hub": (CHAIN_SCRIPT.replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 5.0 3.5 1.0 1.0"), {})}
+assert "bond_style harmonic" in HARMONIC and HARMONIC.count("1.05") == 2 and "3.5 1.0 1.0" in BOND_PATHS["fene-hub"][0]
+
+
+@pytest.mark.parametrize("steps", [0, 60])
+@pytest.mark.parametrize("case", sorted(BOND_PATHS))
+def test_bond_table_paths(tmp_path, monkeypatch, case, steps):
+    """The setup build (`run 0`) and the last rebuild inside a run of 60 steps (in the throughput shape of the step kernel,
+    which bins for the rebuild): the list entry by entry, the number of builds against the oracle's, and the plan."""
+    head, env = BOND_PATHS[case]
+    for k, v in dict(env, **(SHAPES["throughput-shape"] if steps else {})).items():
+        monkeypatch.setenv(k, v)
+    s = I.special_chain(True) if case == "fene-hub" else I.rebuild_chain()
+    script = head + "fix 1 all nve\nfix 2 all langevin 1.0 1.0 1.0 904297\nrun %d\n" % steps
+    lmp, L, x, ref = run_and_check(s, script, tmp_path, current=steps == 0)
+    builds = lmp.stat("neigh_builds")
+    o = run_oracle(script, s)
+    assert builds == o.neigh_builds() and (steps == 0 or builds >= 3)
+    topo = (lmp.gather("num_bond"), lmp.gather("bond_type"), lmp.gather("bond_atom"))
+    bpa, minimg = np.asarray(topo[1]).size // len(x), lmp.stat("bond_minimg")
+    plan = int(lmp.stat("rebuild_plan"))
+    moved = case == "fene-hub"          # the permute writes the table
+    assert minimg == int(moved) and bpa == (6 if moved else 3)
+    later = dict(last_rebuild(script, s, builds, steps), phys_valid=0, bins_ready=1, counts_dirty=1) if steps else {}
+    assert plan == planned(topo, len(x), FENE, minimg, **later)
+    assert bool(plan & P.PERMUTE_BONDS) == moved and bool(plan & P.BOND_TABLE) == (not moved) and bool(plan & P.FROZEN_IMAGES) == (not moved)
+    assert not plan & (P.PERMUTE_PHYS | P.BOND_PACK_PHYS) and bool(plan & P.PREBINNED) == (steps > 0) and bool(plan & P.WRAP_BIN) == (steps == 0)
+    if case == "fene-frozen":          # the same plan as for bonds that cannot do without frozen images
+        monkeypatch.delenv("LAMMPS_LE_FREEZE_IMAGES")
+        assert plan == planned(topo, len(x), FENE, 0, **later)
+    lmp.close()
 
 
 @pytest.mark.parametrize("shape", sorted(SHAPES))
@@ -234,9 +326,17 @@ def test_rebuild_trigger_at_the_edge_of_its_band(tmp_path, sign, shape):
 def test_decomposed(tmp_path, world):
     """Every rank hands out the lists of the beads it owns, ghost neighbors by their tag: the union is the full list."""
     s, meta = I.slab_ladder()
-    ranks = run_in_children(world, s, I.ZERO_SCRIPT + "run 0\n", tmp_path)
+    ranks = run_in_children(world, s, I.ZERO_SCRIPT + "run 0\nrun 0\n", tmp_path)
     assert all(len(r["owned"]) > 0 for r in ranks)
     r0 = ranks[0]
+    # (e) both setup builds on every rank: map[] filled before the first only, nothing prebinned, the decomposed build, the
+    # send lists reordered for direct receive
+    topo = (r0["num_bond"], r0["bond_type"], r0["bond_atom"])
+    dd = dict(decomposed=1, row_tile=0, bond_minimg=r0["bond_minimg"][0])
+    first, second = planned(topo, len(s["x"]), map_stale=1, **dd), planned(topo, len(s["x"]), **dd)
+    assert first == second | P.MAP_FILL and not second & (P.MAP_FILL | P.PREBINNED | P.WRAP_BIN | P.PERMUTE_BONDS)
+    assert (second & P.DDCODE) >> P.DDCODE_SHIFT == 1 and second & P.DIRECT_RECV and second & P.BOND_TABLE
+    assert all(r["rebuild_plan"].tolist() == [first, second] for r in ranks)
     assert sum(len(r["itag"]) for r in ranks) == r0["neigh_pairs"][0]
     check_list(joined(ranks), s, (r0["num_bond"], r0["bond_type"], r0["bond_atom"]), r0["neigh_pairs"][0], FENE, r0["x"])
     # the probes really straddle this run's slab boundaries: some pair has its two beads on different ranks

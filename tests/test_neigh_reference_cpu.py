@@ -133,7 +133,7 @@ def test_ladder_straddles_the_fp32_band(origin):
     s, meta = I.ladder(origin)
     _, x, ref = reference_of("ladder-origin%d" % origin)
     box = np.asarray(s["box"])
-    # the band of the list build, restated from kernels_neigh.hip launch_lists.  If that formula is ever narrowed, the rungs
+    # the band of the list build, restated from kernels_neigh.hip rebuild_lists.  If that formula is ever narrowed, the rungs
     # below (BAND_RUNGS are fractions of THIS band) have to be derived again from the new one.
     M = np.abs(box).max()
     e_d = 8.0 * M * 5.97e-8
