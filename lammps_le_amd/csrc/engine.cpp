@@ -1241,8 +1241,9 @@ void Engine::run(long nsteps) {
   init();
   rebuild_knobs = RebuildKnobs();
   double tr1 = wall();
-  // (a fix on a group that was defined since the last upload: the masks and the member ranks travel with an upload)
-  if (dev && dev_current && fixes_on_groups(this) && group_sig != group_signature()) { download(); dev_current = false; }
+  // (the fixes on groups are not those of the last upload: the masks, the member ranks and the thermostat's member count travel
+  // with an upload - also when the last fix on a group has gone and they have to fall back to `all`)
+  if (dev && dev_current && group_sig != group_signature()) { download(); dev_current = false; }
   if (!dev_current || !dev || !dev->pos) upload();
   group_sig = group_signature();
   if (dev->dd) dd_fast_halo_switch(*dev);

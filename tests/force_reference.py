@@ -240,7 +240,10 @@ Eval = collections.namedtuple("Eval", "f f_pair f_bond f_angle evdwl ebond eangl
 class System:
     """types, masses, box, bonds (type, tag, tag), angles (type, tag, tag, tag) with tags = row + 1."""
 
-    def __init__(self, model, box, types, mass, bonds, angles=None):
+    def __init__(self, model, box, types, mass, bonds, angles=None, special_from=None):
+        """angles: rows, or a multiset {(type, tag, tag, tag): copies} - a duplicate counts twice, as the engines evaluate every
+        stored copy.  special_from: the bonds the special levels are searched over, if not `bonds` (a deliberately stale
+        table, for the tests that show a wrong level moves a force)."""
         self.model = model
         self.units = UNITS[model.units]
         self.box = np.asarray(box, dtype=np.float64)
@@ -249,17 +252,27 @@ class System:
         self.n = n = len(self.types)
         self.ntypes = len(mass)
         self.m = ld([mass[t - 1] for t in self.types])
-        self.bonds = np.asarray(bonds, dtype=np.int64).reshape(-1, 3)
-        self.bonds = self.bonds[[model.bond.get(int(t), ("zero",))[0] != "zero" for t in self.bonds[:, 0]]] if len(self.bonds) else self.bonds
-        self.angles = np.zeros((0, 4), dtype=np.int64) if angles is None or not model.angle else np.asarray(angles, dtype=np.int64).reshape(-1, 4)
         self.norm = (model.units == "lj") if model.norm is None else model.norm
         self.mobile = np.ones(n, dtype=bool) if model.nve_types is None else np.isin(self.types, model.nve_types)
         if model.pair is not None:
-            eps, sig, cut, off = pair_matrix(model, self.ntypes)
-            self.cutmax = float(cut.max())
+            self.pair_coeffs = pair_matrix(model, self.ntypes)
+            self.cutmax = float(self.pair_coeffs[2].max())
+        self.set_topology(bonds, angles, special_from)
+
+    def set_topology(self, bonds, angles=None, special_from=None):
+        """The bonds, the angles and the pair weights that follow from the bond graph (the candidate pairs with them)."""
+        model, n = self.model, self.n
+        graph = np.asarray(bonds if special_from is None else special_from).reshape(-1, 3)
+        self.bonds = np.asarray(bonds, dtype=np.int64).reshape(-1, 3)
+        self.bonds = self.bonds[[model.bond.get(int(t), ("zero",))[0] != "zero" for t in self.bonds[:, 0]]] if len(self.bonds) else self.bonds
+        if isinstance(angles, dict):
+            angles = [row for row, copies in sorted(angles.items()) for _ in range(copies)]
+        self.angles = np.zeros((0, 4), dtype=np.int64) if angles is None or not model.angle else np.asarray(angles, dtype=np.int64).reshape(-1, 4)
+        if model.pair is not None:
+            eps, sig, cut, off = self.pair_coeffs
             iu, ju = np.triu_indices(n, 1)
             w = np.ones(len(iu), dtype=LD)
-            sp = reference_specials(n, np.asarray(bonds).reshape(-1, 3))          # (all bonds of the data file: the graph, not the styles)
+            sp = reference_specials(n, graph)          # (all bonds of the table: the graph, not the styles)
             pos = {}
             for a, lv in sp.items():
                 for b, level in lv.items():
@@ -403,10 +416,13 @@ class System:
     def unwrapped(self, x, img):
         return ld(x) + ld(img) * self.prd
 
-    def trajectory(self, x0, v0, img0, nsteps, uniforms=None):
+    def trajectory(self, x0, v0, img0, nsteps, uniforms=None, topology=None):
         """Velocity Verlet from the state read_data leaves (x0 inside the box, image flags img0): setup, then nsteps steps.
         Returns per step (0 .. nsteps) the unwrapped positions, velocities, thermo rows and min |r^2 - cut^2|, and the
-        force array of the last step (with the Langevin force, as the engine's f holds it)."""
+        force array of the last step (with the Langevin force, as the engine's f holds it).
+        topology(step) -> (bonds, angles): the tables in force at the force evaluation of `step` (a fix that edits them does so
+        between the position update and that evaluation); where the answer differs from the previous step's, the bonds, the
+        angles and the pair weights are rebuilt before the evaluation.  Without it the topology is static."""
         assert self.model.nve
         x, v, img = ld(x0).copy(), ld(v0).copy(), np.asarray(img0, dtype=np.int64).copy()
         dt = LD(self.model.dt)
@@ -415,7 +431,16 @@ class System:
         n3 = 3 * self.n
         xs, vs, rows, gaps, fracs = [], [], [], [], []
 
+        held = [None]
+
         def forces(step):
+            if topology is not None:
+                bonds, angles = topology(step)
+                key = (sorted(map(tuple, np.asarray(bonds).reshape(-1, 3).tolist())),
+                       sorted(angles.items()) if isinstance(angles, dict) else None if angles is None else sorted(map(tuple, np.asarray(angles).reshape(-1, 4).tolist())))
+                if key != held[0]:
+                    self.set_topology(bonds, angles)
+                    held[0] = key
             ev = self.evaluate(x)
             f = ev.f
             if self.model.langevin:

@@ -36,9 +36,11 @@ C = I.CUTNEIGH
 FENE = ((0.0, 1.0, 1.0), (0.0, 1.0, 1.0))
 
 
-def check_list(L, system, topo, neigh_pairs, weights=FENE, x_now=None):
+def check_list(L, system, topo, neigh_pairs, weights=FENE, x_now=None, bonds=None, cutneigh=C):
     """(b), (c), (d) and - with x_now, the engine's current positions - (a).  L: fetch_list() (one rank) or the ranks' lists
-    joined; topo = (num_bond, bond_type, bond_atom) gathered from the same handle.  Returns (x by tag, reference)."""
+    joined; topo = (num_bond, bond_type, bond_atom) gathered from the same handle.  bonds: the bonds the tables have to hold,
+    rows (type, a, b) - the data file's unless a fix has edited them (test_gpu_le_state.py); the special codes always follow
+    the search over the stored bonds.  cutneigh: the list cutoff, if not the chain scripts'.  Returns (x by tag, reference)."""
     n = len(system["x"])
     box = np.asarray(system["box"], dtype=np.float64)
     owned = np.asarray(L["owned"])
@@ -49,23 +51,24 @@ def check_list(L, system, topo, neigh_pairs, weights=FENE, x_now=None):
         assert np.array_equal(x, x_now), "list was not built from the current positions"
         assert np.array_equal(x, wrap_into_box(system)[0])
     assert (x >= box[:, 0]).all() and (x < box[:, 1]).all()
-    ref = R.reference_pairs(x, box, C)
+    ref = R.reference_pairs(x, box, cutneigh)
     assert R.undecided(ref) == []
     num_bond, bond_type, bond_atom = (np.asarray(t).reshape(n, -1) for t in topo)
     stored = collections.Counter()
-    bonds = []
+    graph = []
     for i in np.nonzero(num_bond[:, 0])[0]:
         for m in range(num_bond[i, 0]):
             stored[(int(i) + 1, int(bond_type[i, m]), int(bond_atom[i, m]))] += 1
-            bonds.append((int(bond_type[i, m]), int(i) + 1, int(bond_atom[i, m])))
-    for t, a, b in np.asarray(system["bonds"]).tolist():          # both ends carry the bond
+            graph.append((int(bond_type[i, m]), int(i) + 1, int(bond_atom[i, m])))
+    held = np.asarray(system["bonds"] if bonds is None else bonds).reshape(-1, 3)
+    for t, a, b in held.tolist():          # both ends carry the bond
         assert stored[(a, t, b)] == 1 and stored[(b, t, a)] == 1
-    assert sum(stored.values()) == 2 * len(system["bonds"])
+    assert sum(stored.values()) == 2 * len(held)
     listed_bonds = collections.Counter(zip(L["btag"].tolist(), L["btype"].tolist(), L["bjtag"].tolist()))
     assert listed_bonds == stored, "bond entries differ from the stored bonds"
-    expected = R.expected_entries(ref, np.arange(1, n + 1), n, bonds, *weights)
+    expected = R.expected_entries(ref, np.arange(1, n + 1), n, graph, *weights)
     x_by_tag = np.vstack([np.zeros((1, 3)), x])
-    rep = R.compare((L["itag"], L["jtag"], L["code"]), expected, (x_by_tag, box, C))
+    rep = R.compare((L["itag"], L["jtag"], L["code"]), expected, (x_by_tag, box, cutneigh))
     print("pair entries %d, expected %d, %s" % (len(L["itag"]), len(expected), rep.counts()))
     assert rep.ok, str(rep)
     assert neigh_pairs == len(L["itag"])
