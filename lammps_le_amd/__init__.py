@@ -208,6 +208,28 @@ class lammps(object):
                 out.add((int(bt[i, m]), min(a, b), max(a, b)))
         return out
 
+    def pair_rows(self, cid):
+        """The rows of a local compute (compute property/local, compute pair/local) as a float64 array of shape
+        (rows, columns), one column per attribute of the compute: for the pair kinds the contact list of the current state,
+        ordered by (lower ID, higher ID).  Raises LammpsError when the compute cannot answer (no run yet, or the host copies
+        have replaced the device state)."""
+        rows = self.extract_compute(cid, LMP_STYLE_LOCAL, LMP_SIZE_ROWS)
+        if rows is None:
+            raise LammpsError("no local compute with ID " + cid)
+        cols = self.extract_compute(cid, LMP_STYLE_LOCAL, LMP_SIZE_COLS)
+        width = max(cols, 1)
+        out = np.empty((rows, width))
+        if rows:
+            p = self.lib.lammps_extract_compute(self.lmp, cid.encode(), LMP_STYLE_LOCAL, LMP_TYPE_ARRAY if cols else LMP_TYPE_VECTOR)
+            self._check()
+            if cols:
+                pp = C.cast(p, C.POINTER(C.POINTER(C.c_double)))
+                # (the rows are one contiguous block: row pointers into it)
+                out[:] = np.ctypeslib.as_array(pp[0], shape=(rows, cols))
+            else:
+                out[:, 0] = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_double)), shape=(rows,))
+        return out
+
     def angle_set(self):
         """{(type, a1, a2, a3)} of the copies the CENTRAL atoms store (one per angle), ends ordered."""
         na, at = self.gather("num_angle"), self.gather("angle_type")

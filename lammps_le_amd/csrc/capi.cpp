@@ -389,6 +389,7 @@ static void scatter_subset_impl(Engine *e, const char *fn, const char *name, int
   }
   const int prop = dbl3 ? (k == "x" ? SUBSET_X : SUBSET_V3) : typ ? SUBSET_TYPE : (count == 3 ? SUBSET_IMG3 : SUBSET_IMG1);
   subset_scatter(d, prop, k == "f" ? 1 : 0, count, K, uid.data(), urows.data());
+  e->dev_edits++;          // (what was computed from the device state at this timestep is no longer current)
   if (k == "x") note_positions_replaced(d);
   if (e->host_current) apply_host();       // keep a current host copy current
 }
@@ -489,7 +490,7 @@ void *lammps_extract_compute(void *handle, char *id, int style, int type) {
     const bool thermo_c = c == "thermo_temp" || c == "thermo_pe" || c == "thermo_press";
     if (!thermo_c && !e->computes_local.count(c)) return nullptr;
     Engine::ComputeCache &cc = e->compute_cache[c];
-    const bool fresh = cc.invoked == e->ntimestep && cc.stamp == e->thermo_log.size();
+    const bool fresh = cc.invoked == e->ntimestep && cc.stamp == e->thermo_log.size() && cc.edits == e->dev_edits;
     if (thermo_c) {
       if (style != LMP_STYLE_GLOBAL) return nullptr;                         // no per-atom / local data
       if (type == LMP_TYPE_ARRAY || type == LMP_SIZE_ROWS || type == LMP_SIZE_COLS) return nullptr;   // no array_flag
@@ -522,6 +523,7 @@ void *lammps_extract_compute(void *handle, char *id, int style, int type) {
         cc.size_vector = (int)cc.vector.size();
         cc.invoked = e->ntimestep;
         cc.stamp = e->thermo_log.size();
+        cc.edits = e->dev_edits;
       }
       if (type == LMP_TYPE_SCALAR) result = &cc.scalar;
       else if (type == LMP_TYPE_VECTOR) result = cc.vector.data();
@@ -531,10 +533,31 @@ void *lammps_extract_compute(void *handle, char *id, int style, int type) {
     // compute property/local (btype batom1 batom2): one row per bond, listed once from the lower ID, both atoms in the
     // compute's group (src/compute_property_local.cpp:420-480; the rows dump local writes)
     if (style != LMP_STYLE_LOCAL) return nullptr;
-    if (!fresh) {
+    const Engine::LocalCompute &lc = e->computes_local.at(c);
+    if (lc.kind != Engine::LOCAL_BOND) {
+      // pair rows: from the device list, shared with every compute of the same kind and group (Engine::pair_rows; nothing is
+      // downloaded).  Asked when the list cannot serve, the call sets the error and answers NULL
+      const std::vector<std::string> &attrs = lc.attrs;
+      const Engine::PairRows &R = e->pair_rows(lc);
+      if (!fresh) {
+        const int nc = (int)attrs.size();
+        std::vector<int> col(nc);
+        for (int k = 0; k < nc; k++) col[k] = Engine::pair_row_column(attrs[k]);
+        cc.vector.resize((size_t)R.nrows * nc);
+        for (long r = 0; r < R.nrows; r++)
+          for (int k = 0; k < nc; k++) cc.vector[(size_t)r * nc + k] = Engine::pair_row_value(R, r, col[k]);
+        cc.size_rows = (int)R.nrows;
+        cc.size_cols = nc > 1 ? nc : 0;
+        cc.rows.resize(cc.size_rows);
+        for (int r = 0; r < cc.size_rows; r++) cc.rows[r] = cc.vector.data() + (size_t)r * nc;
+        cc.invoked = e->ntimestep;
+        cc.stamp = e->thermo_log.size();
+        cc.edits = e->dev_edits;
+      }
+    } else if (!fresh) {
       e->download();
-      const std::vector<std::string> &attrs = e->computes_local[c];
-      const int bit = e->computes_local_bit.count(c) ? e->computes_local_bit[c] : 1;
+      const std::vector<std::string> &attrs = lc.attrs;
+      const int bit = lc.bit;
       auto member = [&](int i) { return bit == 1 || (!e->gmask.empty() && (e->gmask[i] & bit)); };
       const int nc = (int)attrs.size();
       cc.vector.clear();
@@ -550,6 +573,7 @@ void *lammps_extract_compute(void *handle, char *id, int style, int type) {
       for (int r = 0; r < cc.size_rows; r++) cc.rows[r] = cc.vector.data() + (size_t)r * nc;
       cc.invoked = e->ntimestep;
       cc.stamp = e->thermo_log.size();
+      cc.edits = e->dev_edits;
     }
     if (type == LMP_TYPE_SCALAR || type == LMP_SIZE_ROWS) result = &cc.size_rows;
     else if (type == LMP_SIZE_COLS) result = &cc.size_cols;
@@ -618,7 +642,7 @@ static const std::vector<std::pair<std::string, std::vector<std::string>>> &styl
   static const std::vector<std::pair<std::string, std::vector<std::string>>> t = {
       {"atom", {"angle", "atomic", "bond", "full", "molecular"}},
       {"bond", {"fene", "harmonic", "hybrid", "none", "zero"}},
-      {"compute", {"property/local"}},
+      {"compute", {"pair/local", "property/local"}},
       {"dump", {"atom", "custom", "dcd", "local"}},
       {"fix", {"bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve"}},
       {"pair", {"lj/cut", "none", "zero"}},
@@ -830,6 +854,10 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "nghost") return e->dev ? (double)e->dev->nghost : 0.0;
   if (k == "fene_warnings") return e->dev && e->dev->flags_h ? (double)e->dev->flags_h[FLAG_FENE_WARN] : 0.0;
   if (k == "bond_minimg") return e->dev ? (double)e->dev->bond_minimg : 0.0;   // bonds take the per-step minimum image (1) or the frozen image words (0), as of the last run
+  if (k == "pair_row_passes") return (double)e->pair_row_passes;        // device passes of the local computes' pair rows so far
+  if (k == "pair_rows") return (double)e->pair_rows_last;              // ... the rows of the last one (whole system)
+  if (k == "pair_rows_count_ms") return e->pair_rows_ms[0];            // ... its count pass + scan, its fill pass + copy (host wall clock)
+  if (k == "pair_rows_fill_ms") return e->pair_rows_ms[1];
   if (k == "host_downloads") return (double)e->host_downloads;          // whole-system downloads (Engine::download)
   if (k == "device_bytes") return e->dev ? (double)e->dev->mem.device_bytes() : 0.0;   // device blocks this handle holds
   if (k == "subset_comm_bytes") return e->subset_comm_bytes;           // this rank's share of the subset calls' collectives

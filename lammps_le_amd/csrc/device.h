@@ -270,7 +270,8 @@ struct DeviceState {
   int *gcell_start = nullptr, *gcell_count = nullptr;   // ghost ranges per cell (relative to n)
   int *sendlist[2] = {nullptr, nullptr};                // owned indices sent down / up every step
   int *sendlist_alt[2] = {nullptr, nullptr};            // ... and the buffers the next rebuild writes its reordered lists into
-  int *gmask = nullptr;                                 // [maxtag+2] group bits by tag (bit 0 = all); only when a fix acts on a group
+  int *gmask = nullptr;                                 // [maxtag+2] group bits by tag (bit 0 = all); only when a fix or a local compute acts on a group
+                                                        // (uploaded with the system; refreshed in place by Engine::pair_rows for a compute defined since)
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
   char *angtab_dev = nullptr;                           // AngleTable in device memory (fused angle step)
   bool ghost_whole_shell = false;                       // every bead within the ghost cutoff of a face is sent (runs with an angle style)
@@ -325,6 +326,11 @@ struct DeviceState {
   size_t ev_used = 0;
   // ---- C-ABI subset calls (kernels_capi.hip): staging block of the K requested rows ----
   char *capi_buf = nullptr;     // grow-only
+  // ---- pair rows of the local computes (kernels_local.hip): counts and row offsets by tag, the rows, their pinned host copy (grow-only) ----
+  int *local_count = nullptr, *local_offset = nullptr;   // [maxtag+2]
+  char *local_scan_tmp = nullptr;
+  char *local_rows = nullptr;       // [R][6] doubles (PAIR kind), then [R][4] ints
+  char *local_rows_h = nullptr;     // pinned
   // owns every pointer (but the mapped peer windows), stream and event above.  The LAST member: destroyed first, while the
   // fields its records point at are still there
   DevMem mem;
@@ -467,6 +473,7 @@ void launch_bond_create(DeviceState &d, const ExLoadParams &p, int rng_slot, con
 void bond_create_counts(DeviceState &d, int *bondcount, int nt);
 void launch_ex_unload(DeviceState &d, const ExUnloadParams &p, int rng_slot);
 void launch_extrusion(DeviceState &d, const ExtrusionParams &p, int rng_slot);
+void dd_halo_wait(DeviceState &d);   // kernels_dd.hip: the main stream waits for a halo in flight on comm_stream
 void stream_sync(DeviceState &d);    // wait for d.stream; with ranks: bounded (Comm::wait_stream)
 void sync_flags(DeviceState &d, unsigned reset_mask = 0);   // copy flags to flags_h, zero the masked ones, wait
 void publish_flags(DeviceState &d, unsigned reset_mask = 0);   // the same without waiting ...
@@ -487,5 +494,15 @@ enum SubsetProp { SUBSET_X = 0, SUBSET_V3 = 1, SUBSET_IMG3 = 2, SUBSET_IMG1 = 3,
 void subset_gather(DeviceState &d, int prop, int which, const int *tab, int count, int K, const int *ids, void *out_rows,
                    int *found);
 void subset_scatter(DeviceState &d, int prop, int which, int count, int K, const int *ids, const void *rows);
+
+// pair rows of compute property/local (NEIGH / PAIR kind) and compute pair/local on this rank (kernels_local.hip): `pair` = the
+// PAIR kind (rsq < cutsq at the current positions, with values), `bit` = the compute's group, `zero` = pair_style zero
+struct LocalRowsRequest {
+  bool pair = false, zero = false;
+  int bit = 1;
+  double zero_cutsq = 0.0;
+  double special_lj[4] = {1.0, 0.0, 0.0, 0.0};
+};
+long local_pair_rows(DeviceState &d, const LocalRowsRequest &rq, const int *&ids, const double *&vals, double ms[2]);
 
 }  // namespace lmp_le

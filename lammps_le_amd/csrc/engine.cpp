@@ -134,6 +134,7 @@ void Engine::init() {
       if (bondtab.style[b] == 0 && nbonds > 0) throw LammpsError("All bond coeffs are not set");
   if (!special_built) build_special();
   for (auto &f : fixes) f->init();
+  init_local_computes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -158,6 +159,7 @@ void Engine::upload() {
                         "not supported by the MI355X engine (minimum-image cell lists)");
   }
   DeviceState &d = *dev;
+  pair_list_ready = false;   // (the lists belong to the arrays of the last rebuild)
   note_order_replaced(d);    // the device arrays are about to be replaced (tag order)
   bool realloc = (d.ntotal != natoms || d.bpa != bpa || d.maxspecial != maxspecial || d.ntypes != ntypes || !d.pos || d.apa != apa);
   double cellcut = cutneighmax > 0.0 ? cutneighmax : std::max({box.prd[0], box.prd[1], box.prd[2]}) / 3.0;
@@ -244,6 +246,7 @@ void Engine::upload() {
       if (f->groupbit != 1) grouped = true;
       if (dynamic_cast<FixLangevin *>(f.get())) lgbit = f->groupbit;
     }
+    for (auto &c : computes_local) if (c.second.bit != 1) grouped = true;     // (the pair rows of a compute on a group test the bits)
     if (grouped) {
       if ((int)gmask.size() != natoms) throw LammpsError("internal: group masks do not match the atom count");
       gm.assign(nt, 0); lr.assign(nt, 0);
@@ -258,6 +261,7 @@ void Engine::upload() {
       DEV_RESERVE(d.mem, d.gmask, nt); DEV_RESERVE(d.mem, d.lgrank, nt);
       up(d.gmask, gm.data(), nt * sizeof(int));
       up(d.lgrank, lr.data(), nt * sizeof(int));
+      gmask_uploaded_version = group_version;
     }
     d.lg_grouped = grouped && lgbit != 1;
     d.lg_bit = lgbit;
@@ -525,6 +529,7 @@ void Engine::reneighbor(bool can_defer, bool sort_due) {
   }
   ago = 0;
   neigh_builds++;
+  pair_list_ready = true;
 }
 
 // Timer::stamp (src/timer.cpp:100-135): wall clock between stamps goes to a section; `timer sync` drains the device first
@@ -703,6 +708,95 @@ double Engine::stat_neigh_pairs() {
   for (int v : nn) s += (v & NN_COUNT_MASK) - ((v >> NN_BOND_SHIFT) & NN_NBOND_MASK);     // pair entries (a bead's bonds open its list)
   if (world > 1) s = comm->allreduce_host_sum(s);
   return s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Pair rows of the local computes (kernels_local.hip).  The device list serves while the device holds the state it was built
+// for: after a run, on a dump step, after C-ABI subset scatters.  It does not before the first run, while the check of a
+// rebuild is pending, or once the host copies have become the state (whole-system scatter, read_data ...): the reference's
+// words for a compute asked between runs for what it cannot give (src/compute.cpp / dump.cpp) are the error then.
+// ---------------------------------------------------------------------------------------------
+const Engine::PairRows &Engine::pair_rows(const LocalCompute &c) {
+  static const char *stale = "Compute used in dump between runs is not current";
+  const int kind = c.kind, bit = c.bit;
+  init_local_compute(c);         // (a compute defined since the last run has not seen its init() checks yet)
+  if (!(pair_lj || pair_zero)) throw LammpsError("No pair style is defined for compute " + c.style);      // (no list without one)
+  if (!dev || !dev_current || !dev->pos || !dev->neigh || reneigh_pending || !pair_list_ready) throw LammpsError(stale);
+  if (world > 1 && dev_edits != dev_edits_at_run) throw LammpsError(stale);      // (ghost copies of a moved bead are not refreshed)
+  for (auto &r : pair_rows_cache)
+    if (r.kind == kind && r.bit == bit && r.step == ntimestep && r.stamp == thermo_log.size() && r.edits == dev_edits) return r;
+  DeviceState &d = *dev;
+  if (bit != 1 && (!d.gmask || gmask_uploaded_version != group_version)) {
+    // the masks on the device are those of the last upload.  No fix reads them: refresh them in place.  Some fix does (its
+    // member ranks travel with an upload as well): the next run brings both
+    for (auto &f : fixes) if (f->groupbit != 1) throw LammpsError(stale);
+    if ((int)gmask.size() != natoms) throw LammpsError("internal: group masks do not match the atom count");
+    std::vector<int> gm((size_t)natoms + 2, 0);
+    std::copy(gmask.begin(), gmask.end(), gm.begin() + 1);
+    DEV_RESERVE(d.mem, d.gmask, gm.size());
+    HIP_CHECK(hipMemcpyAsync(d.gmask, gm.data(), gm.size() * sizeof(int), hipMemcpyHostToDevice, d.stream));
+    stream_sync(d);
+    gmask_uploaded_version = group_version;
+  }
+  LocalRowsRequest rq;
+  rq.pair = kind == LOCAL_PAIR; rq.bit = bit; rq.zero = !pair_lj; rq.zero_cutsq = pair_cut_global * pair_cut_global;
+  for (int k = 0; k < 4; k++) rq.special_lj[k] = special_lj[k];
+  const int *ids = nullptr;
+  const double *vals = nullptr;
+  const long mine = local_pair_rows(d, rq, ids, vals, pair_rows_ms);
+  PairRows *out = nullptr;
+  for (auto &r : pair_rows_cache) if (r.kind == kind && r.bit == bit) out = &r;
+  if (!out) { pair_rows_cache.emplace_back(); out = &pair_rows_cache.back(); }
+  out->kind = kind; out->bit = bit;
+  const size_t nv = rq.pair ? 6 : 0;
+  if (world <= 1) {
+    out->nrows = mine;
+    out->ids.assign(ids, ids + 4 * (size_t)mine);
+    out->vals.assign(vals, vals + nv * (size_t)mine);
+  } else {
+    // counts, then the rows padded to the longest table, all-gathered (the shape of dd_gather_needed); a bead is owned by one
+    // rank, so the ranks' tables - each ordered by (atom1, atom2) - interleave by atom1 without ties
+    const int W = world;
+    std::vector<long> counts(W);
+    comm->allgather_host(&mine, counts.data(), sizeof(long));
+    const long most = *std::max_element(counts.begin(), counts.end());
+    const size_t rowb = 4 * sizeof(int) + nv * sizeof(double), per = (size_t)most * rowb;
+    std::vector<char> send(std::max(per, (size_t)8), 0), recv(std::max(per, (size_t)8) * W);
+    if (mine) memcpy(send.data(), ids, 4 * sizeof(int) * (size_t)mine);
+    if (mine && nv) memcpy(send.data() + 4 * sizeof(int) * (size_t)most, vals, nv * sizeof(double) * (size_t)mine);
+    if (most) comm->allgather_host(send.data(), recv.data(), per);
+    subset_comm_bytes += (double)(sizeof(long) + per);
+    long total = 0;
+    for (long c : counts) total += c;
+    std::vector<std::pair<int, long>> order;      // (rank, row) of every row
+    order.reserve(total);
+    for (int q = 0; q < W; q++) for (long r = 0; r < counts[q]; r++) order.push_back({q, r});
+    auto idrow = [&](const std::pair<int, long> &a) { return (const int *)(recv.data() + per * a.first) + 4 * a.second; };
+    std::sort(order.begin(), order.end(), [&](const std::pair<int, long> &a, const std::pair<int, long> &b) {
+      const int *x = idrow(a), *y = idrow(b);
+      return x[0] != y[0] ? x[0] < y[0] : x[1] < y[1];
+    });
+    out->nrows = total;
+    out->ids.resize(4 * (size_t)total);
+    out->vals.resize(nv * (size_t)total);
+    for (long r = 0; r < total; r++) {
+      memcpy(&out->ids[4 * (size_t)r], idrow(order[r]), 4 * sizeof(int));
+      if (nv) memcpy(&out->vals[nv * (size_t)r], recv.data() + per * order[r].first + 4 * sizeof(int) * (size_t)most + nv * sizeof(double) * (size_t)order[r].second, nv * sizeof(double));
+    }
+  }
+  out->step = ntimestep; out->stamp = thermo_log.size(); out->edits = dev_edits;
+  pair_row_passes++;
+  pair_rows_last = out->nrows;
+  return *out;
+}
+
+// column of a pair-row attribute: 0 .. 3 = atom1 atom2 type1 type2 (PairRows::ids), 4 .. 9 = dist eng force fx fy fz (vals)
+int Engine::pair_row_column(const std::string &a) {
+  static const char *names[] = {"natom1", "natom2", "ntype1", "ntype2", "dist", "eng", "force", "fx", "fy", "fz"};
+  for (int k = 0; k < 10; k++) if (a == names[k]) return k;
+  static const char *pnames[] = {"patom1", "patom2", "ptype1", "ptype2"};
+  for (int k = 0; k < 4; k++) if (a == pnames[k]) return k;
+  throw LammpsError("internal: " + a + " is no column of the pair rows");
 }
 
 // advance the Langevin stream by one post_force call: 3N draws into rng_out (canonical order)
@@ -1274,6 +1368,7 @@ void Engine::run(long nsteps) {
   dev->le_snapshot = 0;
   for (auto &f : fixes) if (f->force_reneighbor) dev->le_snapshot = 1;
   note_topology_changed(*dev);     // bond tables may have been edited between runs
+  dev_edits_at_run = dev_edits;    // (the setup rebuild refreshes every ghost)
   beginstep = ntimestep;
   endstep = ntimestep + nsteps;
   atimestep = ntimestep;            // Integrate::init (src/integrate.cpp:48)
@@ -1292,6 +1387,7 @@ void Engine::run(long nsteps) {
     loop_time = wall() - t0;
     atime += (double)(ntimestep - atimestep) * dt;       // Update::update_time at the end of a run (src/verlet.cpp:362)
     atimestep = ntimestep;
+    dev_edits_at_run = dev_edits;
   } catch (...) {
     // a rank that leaves the loop on an error must not keep its peers inside a collective: tear the communicator down
     // (they end with "communicator aborted" or their own copy of the error; see Comm::wait_stream)

@@ -359,8 +359,43 @@ class Engine {
     FILE *fp = nullptr;
   };
   std::vector<Dump> dumps;
-  std::map<std::string, std::vector<std::string>> computes_local;   // compute ID -> property/local attributes
-  std::map<std::string, int> computes_local_bit;                    // compute ID -> group bit (both atoms of a bond must be members)
+  // what the rows of a local compute are (src/compute_property_local.cpp kindflag): the stored bonds, the pair entries of the
+  // neighbor list (natom1 natom2 ntype1 ntype2), or of those the pairs within their cutoff at the current positions (patom1
+  // patom2 ptype1 ptype2, and every value of compute pair/local: dist eng force fx fy fz)
+  enum { LOCAL_BOND = 0, LOCAL_NEIGH = 1, LOCAL_PAIR = 2 };
+  struct LocalCompute {
+    std::string style;                 // "property/local" | "pair/local"
+    int kind = LOCAL_BOND;             // LOCAL_*: what its rows are
+    int bit = 1;                       // group bit: both atoms of a row must be members
+    std::vector<std::string> attrs;    // its columns, as named in the command
+  };
+  std::map<std::string, LocalCompute> computes_local;               // by compute ID
+  void compute_command(std::vector<std::string> &arg);
+  // the checks of a compute's init(): at every run for every compute, and before a compute defined since answers
+  void init_local_compute(const LocalCompute &c) const;
+  void init_local_computes() const { for (auto &c : computes_local) init_local_compute(c.second); }
+  // Pair rows (kernels_local.hip): one device pass per (kind, group) and state, shared by every compute and dump column that
+  // asks for it.  A state is (timestep, thermo rows so far, edits of the device state through the C-ABI subset calls).
+  struct PairRows {
+    int kind = LOCAL_NEIGH, bit = 1;
+    long step = -1, edits = -1;
+    size_t stamp = 0;
+    long nrows = 0;
+    std::vector<int> ids;        // [nrows][4] atom1 atom2 type1 type2, ordered by (atom1, atom2)
+    std::vector<double> vals;    // [nrows][6] dist eng force fx fy fz (LOCAL_PAIR)
+  };
+  std::vector<PairRows> pair_rows_cache;
+  const PairRows &pair_rows(const LocalCompute &c);  // collective when decomposed: every rank ends with the whole table
+  static int pair_row_column(const std::string &attr);
+  static double pair_row_value(const PairRows &r, long row, int column) {
+    return column < 4 ? (double)r.ids[4 * (size_t)row + column] : r.vals[6 * (size_t)row + (column - 4)];
+  }
+  bool pair_list_ready = false;  // the device holds a neighbor list built for the arrays it holds (set by reneighbor, cleared by upload)
+  long dev_edits = 0;            // C-ABI subset scatters applied to the device state so far
+  long dev_edits_at_run = 0;     // ... as of the end of the last run (decomposed: ghosts are current up to there)
+  long group_version = 0, gmask_uploaded_version = -1;   // `group` commands so far; the version DeviceState::gmask holds
+  long pair_row_passes = 0, pair_rows_last = 0;          // device passes so far, rows of the last one (lammps_le_stat)
+  double pair_rows_ms[2] = {0.0, 0.0};                   // the last pass: count + scan, fill + copy (host wall clock)
   // ---- restart: own binary format, bit-continuous incl. the RNG streams of the fixes ----
   void write_restart(const std::string &path);
   void read_restart(const std::string &path);
@@ -432,6 +467,7 @@ class Engine {
   struct ComputeCache {
     long invoked = -1;                 // ntimestep of the evaluation ...
     size_t stamp = 0;                  // ... and thermo_log.size() then (a run in between re-evaluates)
+    long edits = -1;                   // ... and Engine::dev_edits then (a subset scatter in between re-evaluates)
     double scalar = 0.0;
     std::vector<double> vector;        // global vector, or property/local values (rows x cols)
     std::vector<double *> rows;        // property/local with several attributes: row pointers (array_local)

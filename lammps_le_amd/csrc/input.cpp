@@ -608,21 +608,11 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     if (box_exist) throw LammpsError("Cannot read_restart after simulation box is defined");   // src/read_restart.cpp:60
     read_restart(arg[0]);
   } else if (cmd == "compute") {
-    // compute ID group property/local attr...   (src/compute_property_local.cpp:30-180; bond attributes only)
-    need(4);
-    const int cbit = group_bit(arg[1]);
-    if (!cbit) throw LammpsError("Could not find compute group ID");         // src/compute.cpp:63-64
-    if (arg[2] != "property/local") throw LammpsError("Unknown compute style " + arg[2]);
-    std::vector<std::string> attrs(arg.begin() + 3, arg.end());
-    for (auto &a : attrs)
-      if (a != "btype" && a != "batom1" && a != "batom2")
-        throw LammpsError("MI355X engine: compute property/local supports btype batom1 batom2 (got " + a + ")");
-    computes_local[arg[0]] = attrs;
-    computes_local_bit[arg[0]] = cbit;
+    compute_command(arg);
   } else if (cmd == "uncompute") {
     need(1);
     if (!computes_local.erase(arg[0])) throw LammpsError("Could not find uncompute ID");
-    computes_local_bit.erase(arg[0]);
+    compute_cache.erase(arg[0]);
   } else if (cmd == "dump") {
     // dump ID group style N file args   (src/dump.cpp:60-170, dump_custom.cpp:60-250, dump_local.cpp:40-130)
     need(5);
@@ -657,7 +647,7 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
           std::string cid = a.substr(2, lb - 2);
           if (!computes_local.count(cid)) throw LammpsError("Could not find dump local compute ID");
           int col = atoi(a.substr(lb + 1, rb - lb - 1).c_str());
-          if (col < 1 || col > (int)computes_local[cid].size()) throw LammpsError("Dump local compute vector is accessed out-of-range");
+          if (col < 1 || col > (int)computes_local[cid].attrs.size()) throw LammpsError("Dump local compute vector is accessed out-of-range");
         }
         dp.cols.push_back(a);
       }
@@ -1463,12 +1453,13 @@ void Engine::group_command(std::vector<std::string> &arg) {
     throw LammpsError("MI355X engine: group style " + style + " is not supported");
   download();
   if (gmask.empty()) gmask.assign(natoms, 1);
+  group_version++;
   int bit = group_bit(name);
   if (style == "delete" || style == "clear") {        // src/group.cpp:103-150
     if (!bit) throw LammpsError("Could not find group " + style + " group ID");
     if (style == "delete") {
       for (auto &f : fixes) if (f->groupbit == bit) throw LammpsError("Cannot delete group currently used by a fix");
-      for (auto &c : computes_local_bit) if (c.second == bit) throw LammpsError("Cannot delete group currently used by a compute");
+      for (auto &c : computes_local) if (c.second.bit == bit) throw LammpsError("Cannot delete group currently used by a compute");
       for (auto &dp : dumps) if (dp.groupbit == bit) throw LammpsError("Cannot delete group currently used by a dump");
     }
     for (int i = 0; i < natoms; i++) gmask[i] &= ~bit;
@@ -1696,6 +1687,76 @@ void Engine::write_data(const std::string &path) {
 
 
 // ---------------------------------------------------------------------------------------------
+// compute ID group property/local attr ... [cutoff type]     (src/compute_property_local.cpp:34-270)
+// compute ID group pair/local value ... [cutoff type]        (src/compute_pair_local.cpp:37-102)
+// The reference's grammar: attributes up to the first word that is none, then options; one kind of attribute per compute.
+// ---------------------------------------------------------------------------------------------
+void Engine::compute_command(std::vector<std::string> &arg) {
+  if (arg.size() < 3) throw LammpsError("Illegal compute command");                  // src/compute.cpp:44
+  const int cbit = group_bit(arg[1]);
+  if (!cbit) throw LammpsError("Could not find compute group ID");                   // src/compute.cpp:63-64
+  const std::string &style = arg[2];
+  if (style != "property/local" && style != "pair/local") throw LammpsError("Unknown compute style " + style);
+  const std::string what = "compute " + style;
+  if (arg.size() < 4) throw LammpsError("Illegal " + what + " command");
+  std::vector<std::string> attrs;
+  int kind = -1;
+  size_t k = 3;
+  if (style == "property/local") {
+    static const char *bond_a[] = {"btype", "batom1", "batom2"}, *neigh_a[] = {"natom1", "natom2", "ntype1", "ntype2"},
+                      *pair_a[] = {"patom1", "patom2", "ptype1", "ptype2"};
+    static const char *other_a[] = {"aatom1", "aatom2", "aatom3", "atype", "datom1", "datom2", "datom3", "datom4", "dtype",
+                                    "iatom1", "iatom2", "iatom3", "iatom4", "itype"};
+    for (; k < arg.size(); k++) {
+      int ak = -1;
+      for (auto a : bond_a) if (arg[k] == a) ak = LOCAL_BOND;
+      for (auto a : neigh_a) if (arg[k] == a) ak = LOCAL_NEIGH;
+      for (auto a : pair_a) if (arg[k] == a) ak = LOCAL_PAIR;
+      for (auto a : other_a)
+        if (arg[k] == a) throw LammpsError("MI355X engine: compute property/local attribute " + arg[k] + " is not supported");
+      if (ak < 0) break;
+      if (kind >= 0 && kind != ak) throw LammpsError("Compute property/local cannot use these inputs together");
+      kind = ak;
+      attrs.push_back(arg[k]);
+    }
+  } else {
+    kind = LOCAL_PAIR;
+    for (; k < arg.size(); k++) {
+      const std::string &a = arg[k];
+      if (a == "dist" || a == "eng" || a == "force" || a == "fx" || a == "fy" || a == "fz") attrs.push_back(a);
+      else if (a[0] == 'p') {
+        if (atoi(a.c_str() + 1) <= 0) throw LammpsError("Invalid keyword in compute pair/local command");
+        attrs.push_back("p" + std::to_string(atoi(a.c_str() + 1)));      // an extra field of Pair::single: refused at the run
+      } else break;
+    }
+  }
+  for (; k < arg.size(); k += 2) {                // optional args
+    if (arg[k] != "cutoff" || k + 2 > arg.size()) throw LammpsError("Illegal " + what + " command");
+    if (arg[k + 1] == "radius") throw LammpsError("Compute " + style + " requires atom attribute radius");
+    if (arg[k + 1] != "type") throw LammpsError("Illegal " + what + " command");
+  }
+  if (attrs.empty()) throw LammpsError("Illegal " + what + " command");
+  LocalCompute &c = computes_local[arg[0]];
+  c.style = style; c.kind = kind; c.bit = cbit; c.attrs = attrs;
+  compute_cache.erase(arg[0]);
+}
+
+// ComputePropertyLocal::init (src/compute_property_local.cpp:273-280), ComputePairLocal::init (compute_pair_local.cpp:116-126)
+void Engine::init_local_compute(const LocalCompute &c) const {
+  if (c.kind == LOCAL_BOND) return;
+  const bool has_pair = pair_lj || pair_zero;
+  if (c.style == "property/local") {
+    if (!has_pair) throw LammpsError("No pair style is defined for compute property/local");
+    return;
+  }
+  bool single = false;
+  for (auto &a : c.attrs) if (a != "dist") single = true;
+  if (single && !has_pair) throw LammpsError("No pair style is defined for compute pair/local");
+  for (auto &a : c.attrs)      // p1 .. pN: lj/cut and zero have no extra fields (Pair::single_extra = 0)
+    if (a[0] == 'p') throw LammpsError("Pair style does not have extra field requested by compute pair/local");
+}
+
+// ---------------------------------------------------------------------------------------------
 // dumps: text snapshots in the reference's formats (header_item: src/dump_custom.cpp:510-527, dump_local.cpp:255-279;
 // values "%d" / "%g" separated by one blank, no trailing blank: dump_custom.cpp:160-170, 280-304).  Rows are in
 // atom-ID order, which is the reference's order at 1 rank with `atom_modify sort 0 0` (or `dump_modify sort id`).
@@ -1706,12 +1767,73 @@ bool Engine::dump_due(long step) const {
 }
 void Engine::write_dumps(long step) {
   if (!dump_due(step)) return;
+  // the compute a `dump local` column names, and the kind of its rows
+  auto col_compute = [&](const std::string &a) { return a.substr(2, a.find('[') - 2); };
+  auto col_kind = [&](const std::string &a) { return computes_local.at(col_compute(a)).kind; };
+  // a dump local whose compute columns are all pair rows of the device list needs no host copy of the system (one without
+  // any compute column lists the bonds, as a dump of bond columns does)
+  bool need_host = false;
+  for (auto &dp : dumps) {
+    if (step % dp.every != 0 || dp.last == step) continue;
+    int pair_cols = 0, bond_cols = 0;
+    if (dp.style == "local")
+      for (auto &a : dp.cols) if (a != "index") (col_kind(a) == LOCAL_BOND ? bond_cols : pair_cols)++;
+    if (!(pair_cols > 0 && bond_cols == 0)) need_host = true;
+  }
   host_current = false;       // mid-run: the device holds the state of this step
-  download();                 // collective when decomposed; every rank then holds the whole system
+  if (need_host) download();  // collective when decomposed; every rank then holds the whole system
   host_current = false;
   for (auto &dp : dumps) {
     if (step % dp.every != 0 || dp.last == step) continue;
     dp.last = step;
+    auto member = [&](int i, int bit) { return bit == 1 || (!gmask.empty() && (gmask[i] & bit)); };
+    long nrows = 0;
+    if (dp.style == "local")    // pair rows: one device pass per (kind, group), collective when decomposed (every rank takes part)
+      for (auto &a : dp.cols) if (a != "index" && col_kind(a) != LOCAL_BOND) pair_rows(computes_local.at(col_compute(a)));
+    // dump local: every column is a column of a local compute; the rows of a column are its compute's (bonds of its group,
+    // or pair rows of its kind and group), and all columns of one dump must have the same number of them (dump_local.cpp:284-325)
+    struct LocalCol { int kind = -1; int bit = 1; std::string attr; int column = 0; const PairRows *rows = nullptr; };
+    std::vector<LocalCol> lcols;
+    std::map<int, std::vector<std::array<int, 3>>> bonds_of;     // group bit -> (type, atom1, atom2) as compute property/local lists them
+    auto bonds_in = [&](int bit) -> std::vector<std::array<int, 3>> & {
+      if (!bonds_of.count(bit)) {
+        // newton_bond off storage: every bond sits with both atoms, listed once from the lower ID
+        // (src/compute_property_local.cpp:420-470)
+        auto &bonds = bonds_of[bit];
+        for (int i = 0; i < natoms; i++)
+          for (int m = 0; m < num_bond[i]; m++) {
+            int bt = bond_type[(size_t)i * bpa + m], j = bond_atom[(size_t)i * bpa + m];
+            if (bt == 0 || i + 1 > j) continue;
+            if (!member(i, bit) || !member(j - 1, bit)) continue;       // (both atoms in the compute's group: :477-480)
+            bonds.push_back({bt, i + 1, j});
+          }
+      }
+      return bonds_of[bit];
+    };
+    if (dp.style == "local") {
+      nrows = -1;
+      for (auto &a : dp.cols) {
+        LocalCol lc;
+        if (a != "index") {
+          const LocalCompute &c = computes_local.at(col_compute(a));
+          size_t lb = a.find('['), rb = a.find(']');
+          lc.kind = c.kind;
+          lc.bit = c.bit;
+          lc.attr = c.attrs[atoi(a.substr(lb + 1, rb - lb - 1).c_str()) - 1];
+          long count;
+          if (lc.kind == LOCAL_BOND) count = (long)bonds_in(lc.bit).size();
+          else {
+            lc.rows = &pair_rows(c);       // (computed above: the cache answers)
+            lc.column = pair_row_column(lc.attr);
+            count = lc.rows->nrows;
+          }
+          if (nrows >= 0 && count != nrows) throw LammpsError("Dump local count is not consistent across input fields");
+          nrows = count;
+        }
+        lcols.push_back(lc);
+      }
+      if (nrows < 0) nrows = (long)bonds_in(1).size();      // no compute column: one row per bond
+    }
     if (rank != 0) continue;
     FILE *fp = dp.fp;
     size_t star = dp.path.find('*');
@@ -1761,24 +1883,7 @@ void Engine::write_dumps(long step) {
       fflush(fp);
       continue;
     }
-    auto member = [&](int i, int bit) { return bit == 1 || (!gmask.empty() && (gmask[i] & bit)); };
-    long nrows = 0;
-    for (int i = 0; i < natoms; i++) nrows += member(i, dp.groupbit) ? 1 : 0;
-    std::vector<std::array<int, 3>> bonds;     // (type, atom1, atom2) as compute property/local lists them
-    if (dp.style == "local") {
-      int cbit = 1;                            // rows come from the computes (all columns of one dump: equal counts, dump_local.cpp:284-325)
-      for (auto &a : dp.cols) if (a != "index") { cbit = computes_local_bit.at(a.substr(2, a.find('[') - 2)); break; }
-      // newton_bond off storage: every bond sits with both atoms, listed once from the lower ID
-      // (src/compute_property_local.cpp:420-470)
-      for (int i = 0; i < natoms; i++)
-        for (int m = 0; m < num_bond[i]; m++) {
-          int bt = bond_type[(size_t)i * bpa + m], j = bond_atom[(size_t)i * bpa + m];
-          if (bt == 0 || i + 1 > j) continue;
-          if (!member(i, cbit) || !member(j - 1, cbit)) continue;       // (both atoms in the compute's group: :477-480)
-          bonds.push_back({bt, i + 1, j});
-        }
-      nrows = (long)bonds.size();
-    }
+    if (dp.style != "local") for (int i = 0; i < natoms; i++) nrows += member(i, dp.groupbit) ? 1 : 0;
     fprintf(fp, "ITEM: TIMESTEP\n%ld\n", step);
     fprintf(fp, "ITEM: NUMBER OF %s\n%ld\n", dp.style == "local" ? dp.label.c_str() : "ATOMS", nrows);
     fprintf(fp, "ITEM: BOX BOUNDS pp pp pp\n");
@@ -1788,19 +1893,13 @@ void Engine::write_dumps(long step) {
     fprintf(fp, "ITEM: %s %s\n", dp.style == "local" ? dp.label.c_str() : "ATOMS", columns.c_str());
     const size_t nc = dp.cols.size();
     if (dp.style == "local") {
-      struct Col { int kind; int attr; };   // kind 0 = index, 1 = compute column
-      std::vector<Col> cc;
-      for (auto &a : dp.cols) {
-        if (a == "index") { cc.push_back({0, 0}); continue; }
-        size_t lb = a.find('['), rb = a.find(']');
-        auto &attrs = computes_local.at(a.substr(2, lb - 2));
-        const std::string &at = attrs[atoi(a.substr(lb + 1, rb - lb - 1).c_str()) - 1];
-        cc.push_back({1, at == "btype" ? 0 : at == "batom1" ? 1 : 2});
-      }
       for (long r = 0; r < nrows; r++)
         for (size_t k = 0; k < nc; k++) {
-          if (cc[k].kind == 0) fprintf(fp, "%ld", r + 1);
-          else fprintf(fp, "%g", (double)bonds[r][cc[k].attr]);     // compute values are doubles
+          const LocalCol &lc = lcols[k];
+          if (lc.kind < 0) fprintf(fp, "%ld", r + 1);
+          else if (lc.kind == LOCAL_BOND)      // compute values are doubles
+            fprintf(fp, "%g", (double)bonds_of[lc.bit][r][lc.attr == "btype" ? 0 : lc.attr == "batom1" ? 1 : 2]);
+          else fprintf(fp, "%g", pair_row_value(*lc.rows, r, lc.column));
           fputc(k + 1 < nc ? ' ' : '\n', fp);
         }
     } else {
