@@ -388,9 +388,11 @@ static void scatter_subset_impl(Engine *e, const char *fn, const char *name, int
     return;
   }
   const int prop = dbl3 ? (k == "x" ? SUBSET_X : SUBSET_V3) : typ ? SUBSET_TYPE : (count == 3 ? SUBSET_IMG3 : SUBSET_IMG1);
+  // (before the rows land: d.pos may have to leave the buffer that records the build - a new type is written into pos.w)
+  if (k == "x") note_positions_replaced(d);
+  else if (typ) detach_positions(d);
   subset_scatter(d, prop, k == "f" ? 1 : 0, count, K, uid.data(), urows.data());
   e->dev_edits++;          // (what was computed from the device state at this timestep is no longer current)
-  if (k == "x") note_positions_replaced(d);
   if (e->host_current) apply_host();       // keep a current host copy current
 }
 

@@ -98,7 +98,8 @@ void dev_alloc(DeviceState &d, int n, int maxtag, int ntypes, int bpa, int maxsp
   if (!d.dd) d.zlo_ext = box.lo[2];
   d.row_tile = (d.dd || getenv("LAMMPS_LE_NO_ROW_TILES")) ? 0 : ROW_TILE;      // (row_id relies on it being ROW_TILE or 0)
   size_t np = d.npad, nt = (size_t)maxtag + 2;
-  DEV_ALLOC(d.mem, d.pos, np); DEV_ALLOC(d.mem, d.pos_tmp, np); DEV_ALLOC(d.mem, d.xhold, np); DEV_ALLOC(d.mem, d.posf, np);
+  DEV_ALLOC(d.mem, d.pos, np); DEV_ALLOC(d.mem, d.pos_tmp, np); DEV_ALLOC(d.mem, d.pos_hold, np); DEV_ALLOC(d.mem, d.posf, np);
+  d.xhold = d.pos_hold; d.step_rotated = false;
   for (int k = 0; k < 3; k++) { DEV_ALLOC(d.mem, d.v[k], np); DEV_ALLOC(d.mem, d.v_tmp[k], np); DEV_ALLOC(d.mem, d.f[k], np); }
   DEV_ALLOC(d.mem, d.tag, np); DEV_ALLOC(d.mem, d.tag_tmp, np);
   DEV_ALLOC(d.mem, d.img, 3 * np); DEV_ALLOC(d.mem, d.img_tmp, 3 * np);
@@ -191,7 +192,21 @@ void dev_free(DeviceState &d) {
   // words that describe freed memory
   d.rng_out = nullptr; d.gather_recv = nullptr; d.halo_flag = nullptr;
   d.rng_W = 0; d.rng_batch_raw[0] = d.rng_batch_raw[1] = 0;
+  d.xhold = nullptr; d.step_rotated = false;
   note_positions_replaced(d);
+}
+
+void detach_positions(DeviceState &d) {
+  if (!d.xhold_alias || !d.pos || d.xhold != d.pos) return;
+  HIP_CHECK(hipMemcpyAsync(d.pos_hold, d.pos, (size_t)d.npad * sizeof(double4), hipMemcpyDeviceToDevice, d.stream));
+  std::swap(d.pos, d.pos_hold);      // (xhold keeps naming the buffer of the build, now held by pos_hold)
+}
+void set_xhold_alias(DeviceState &d, bool on) {
+  if (!on && d.pos && d.xhold == d.pos) {
+    HIP_CHECK(hipMemcpyAsync(d.pos_hold, d.pos, (size_t)d.npad * sizeof(double4), hipMemcpyDeviceToDevice, d.stream));
+    d.xhold = d.pos_hold;
+  }
+  d.xhold_alias = on;
 }
 
 // flags reach the host through a mapped pinned page written by a one-wave kernel (a blit-copy of 64 bytes costs

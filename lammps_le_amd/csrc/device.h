@@ -145,7 +145,17 @@ struct DeviceState {
 
   // ---- physical order ----
   double4 *pos = nullptr, *pos_tmp = nullptr;   // x y z type
-  double4 *xhold = nullptr;                      // positions at the last build (same order)
+  double4 *pos_hold = nullptr;                   // the third position buffer (see xhold)
+  // positions at the last build (same order): a VIEW, the registry does not know it.  Decomposed runs, and every run under
+  // LAMMPS_LE_NO_XHOLD_ALIAS=1: xhold == pos_hold, the rebuild stores a copy there.  One GPU otherwise (xhold_alias): the
+  // buffer k_permute wrote IS the record - xhold names it, and the step kernels ping-pong between the other two, so
+  // xhold == pos until the first step after a build and xhold == pos_hold from then on, never pos_tmp.  Whoever writes d.pos
+  // in place goes through note_positions_replaced first, which moves d.pos off that buffer (detach_positions).  The one
+  // exception: k_exload_create stores a bead's new TYPE into pos[p].w in the middle of a firing step, alias or not; under
+  // the alias xhold[p].w follows it.  Nothing reads the w of xhold (the displacement tests and the LE fixes take x y z).
+  double4 *xhold = nullptr;
+  bool xhold_alias = false;
+  bool step_rotated = false;                     // the last launch_step rotated three buffers, not two (undo_step_swap)
   float4 *posf = nullptr;                        // FP32 copy of the positions at the last reneighbor (list-build distance test)
   double *v[3] = {nullptr, nullptr, nullptr}, *v_tmp[3] = {nullptr, nullptr, nullptr};
   double *f[3] = {nullptr, nullptr, nullptr};
@@ -194,6 +204,7 @@ struct DeviceState {
   double cellinv[3] = {0, 0, 0};
   int *cell_of = nullptr, *cell_count = nullptr, *cell_start = nullptr;
   int *scan_tmp = nullptr, *perm = nullptr;
+  bool scan_two_pass = false;                    // LAMMPS_LE_SCAN_TWO_PASS=1: the cell scans one count per thread (k_scan_local + k_scan_add)
   int maxneigh = 0;
   int *neigh = nullptr;      // [maxneigh][npad] full list, special bits in the top 2 bits
   int *numneigh = nullptr;   // [npad]
@@ -399,7 +410,24 @@ void scan_cells(DeviceState &d, int *count, int *start, int nc, int total);   //
 // The flags of DeviceState a rebuild plans from (bins_ready, cell_count_dirty, bond_pack_dirty, bond_pack_p_valid, topo_dirty,
 // map_stale) are raised from outside the rebuild through these and cleared by the rebuild's stages alone.
 inline void note_topology_changed(DeviceState &d) { d.topo_dirty = d.bond_pack_dirty = d.angle_pack_dirty = true; }   // bond / angle tables edited
-inline void note_positions_replaced(DeviceState &d) { d.bins_ready = false; }     // bins a step kernel left behind belong to the old positions
+// xhold_alias: d.pos leaves the buffer that records the build (copy into the free buffer, on the stream) - before anything
+// writes d.pos in place.  A no-op once a step kernel has run since the build, i.e. on every plain step.
+void detach_positions(DeviceState &d);
+// positions are about to be written in place, or replaced: bins a step kernel left behind belong to the old positions
+inline void note_positions_replaced(DeviceState &d) { d.bins_ready = false; detach_positions(d); }
+// a launch of the step kernel moved on to the other position buffer; the one that records the build is never the next target
+inline void note_step_swapped(DeviceState &d) {
+  std::swap(d.pos, d.pos_tmp);
+  d.step_rotated = d.pos_tmp == d.xhold;
+  if (d.step_rotated) std::swap(d.pos_tmp, d.pos_hold);
+}
+inline void undo_step_swap(DeviceState &d) {       // the launch stored nothing (a list had overflowed): back to the state before it
+  if (d.step_rotated) std::swap(d.pos_tmp, d.pos_hold);
+  std::swap(d.pos, d.pos_tmp);
+  d.step_rotated = false;
+}
+// Engine::run, once per `run` command: the mode of this run.  Leaving the alias mode gives xhold its own buffer back.
+void set_xhold_alias(DeviceState &d, bool on);
 inline void note_order_replaced(DeviceState &d) { d.bins_ready = false; d.bond_pack_p_valid = false; }   // the arrays are (about to be) refilled in another order
 inline void note_arrays_allocated(DeviceState &d) {      // dev_alloc: zeroed cell counts, no packed records yet
   note_order_replaced(d);

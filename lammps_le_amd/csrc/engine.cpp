@@ -223,6 +223,7 @@ void Engine::upload() {
   auto up = [&](void *dst, const void *src, size_t bytes) {
     HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d.stream));
   };
+  d.xhold = d.pos_hold;      // (an upload starts the rotation of the position buffers afresh: device.h xhold)
   up(d.pos, pos.data(), np * sizeof(double4));
   up(d.xhold, pos.data(), np * sizeof(double4));
   for (int k = 0; k < 3; k++) {
@@ -1114,7 +1115,7 @@ void Engine::iterate(long nsteps) {
         if (!finish_reneighbor()) {
           // a list of the build that preceded this launch overflowed: the kernel saw the flag and stored nothing.
           // Undo the launch on the host side, grow the table, rebuild, launch again.
-          if (next) std::swap(d.pos, d.pos_tmp);
+          if (next) undo_step_swap(d);
           regrow_lists();
           if (plan.ang && !next) launch_angle(d, angtab, false, true);
           launch_step(d, plan, sa);
@@ -1342,6 +1343,8 @@ void Engine::run(long nsteps) {
   group_sig = group_signature();
   if (dev->dd) dd_fast_halo_switch(*dev);
   for (int k = 1; k <= 3; k++) dev->sflag[k] = special_flag(k);
+  set_xhold_alias(*dev, !dev->dd && !rebuild_knobs.no_xhold_alias);
+  dev->scan_two_pass = rebuild_knobs.scan_two_pass;
   dev->ident_order = local_order_is_tag_order();
   {
     // bond partner images: frozen at the reneighbor as in the reference (src/ntopo_bond_all.cpp:52-73), unless the minimum

@@ -1026,7 +1026,7 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
     launch_step_kernel(d, q, R, a, nullptr, nullptr);
   }
   launch_step_kernel(d, p, A, a, a.ev_start, a.ev_stop);
-  if (p.next && a.swap_buffers) std::swap(d.pos, d.pos_tmp);
+  if (p.next && a.swap_buffers) note_step_swapped(d);
 }
 // test hook (not part of the reference surface, not declared in include/lammps_le.h): the plan for a request under the
 // environment switches as they stand at this call.  req = langevin, next, ident, pair, angles, thermo, nvebit, lgbit, which,

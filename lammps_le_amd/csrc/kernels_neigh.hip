@@ -98,6 +98,65 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_add(int m, int *__restrict_
   if (i == 0) out[m] = total_slot_n;
 }
 
+// ---- the same scan, four counts per thread ----
+// A thread takes four consecutive counts with one 16-byte load (zeroed as read, one 16-byte store), a block SCAN_SPAN cells:
+// a quarter of the blocks and of the memory instructions of the pair above (LAMMPS_LE_SCAN_TWO_PASS=1 keeps that pair).
+constexpr int SCAN_SPAN = 4 * SCAN_BLOCK;
+__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_local4(int m, int *__restrict__ in, int *__restrict__ out,
+                                                            int *__restrict__ blocksum) {
+  __shared__ int wtot[SCAN_BLOCK / 64];
+  const int i = blockIdx.x * SCAN_SPAN + 4 * threadIdx.x;
+  int4 c = make_int4(0, 0, 0, 0);
+  const bool whole = i + 3 < m;
+  if (whole) {
+    c = *reinterpret_cast<const int4 *>(in + i);
+    *reinterpret_cast<int4 *>(in + i) = make_int4(0, 0, 0, 0);
+  } else {      // the tail of the array, count by count
+    if (i < m) { c.x = in[i]; in[i] = 0; }
+    if (i + 1 < m) { c.y = in[i + 1]; in[i + 1] = 0; }
+    if (i + 2 < m) { c.z = in[i + 2]; in[i + 2] = 0; }
+  }
+  const int v = c.x + c.y + c.z + c.w;
+  const int inc = wave_inclusive_scan(v);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 63) wtot[w] = inc;
+  __syncthreads();
+  int before = 0;
+  for (int k = 0; k < w; k++) before += wtot[k];
+  const int ex = before + inc - v;
+  const int4 o = make_int4(ex, ex + c.x, ex + c.x + c.y, ex + c.x + c.y + c.z);
+  if (whole) *reinterpret_cast<int4 *>(out + i) = o;
+  else {
+    if (i < m) out[i] = o.x;
+    if (i + 1 < m) out[i + 1] = o.y;
+    if (i + 2 < m) out[i + 2] = o.z;
+  }
+  if (threadIdx.x == SCAN_BLOCK - 1) blocksum[blockIdx.x] = before + inc;
+}
+__global__ __launch_bounds__(SCAN_BLOCK) void k_scan_add4(int m, int *__restrict__ out, const int *__restrict__ blocksum,
+                                                          int total_slot_n) {
+  __shared__ int wtot[SCAN_BLOCK / 64];
+  int part = 0;
+  for (int b = threadIdx.x; b < (int)blockIdx.x; b += SCAN_BLOCK) part += blocksum[b];
+  part = wave_sum(part);
+  if ((threadIdx.x & 63) == 0) wtot[threadIdx.x >> 6] = part;
+  __syncthreads();
+  int offset = 0;
+#pragma unroll
+  for (int k = 0; k < SCAN_BLOCK / 64; k++) offset += wtot[k];
+  const int i = blockIdx.x * SCAN_SPAN + 4 * threadIdx.x;
+  if (i + 3 < m) {
+    int4 o = *reinterpret_cast<const int4 *>(out + i);
+    o.x += offset; o.y += offset; o.z += offset; o.w += offset;
+    *reinterpret_cast<int4 *>(out + i) = o;
+  } else {
+    if (i < m) out[i] += offset;
+    if (i + 1 < m) out[i + 1] += offset;
+    if (i + 2 < m) out[i + 2] += offset;
+  }
+  if (i == 0) out[m] = total_slot_n;
+}
+
 __global__ __launch_bounds__(BLOCK) void k_scatter(int n, const int *__restrict__ cell_of,
                                                    const int *__restrict__ cell_start, const int *__restrict__ rank,
                                                    int *__restrict__ perm) {
@@ -201,7 +260,7 @@ __global__ __launch_bounds__(BLOCK) void k_permute(int n, int npad, const int *_
   int dix = 0, diy = 0, diz = 0;
   if (wrap) wrap_into_box(r, box, dix, diy, diz);   // the step kernel binned these positions: Domain::pbc is applied here
   pos_new[s] = r;
-  xhold[s] = r;
+  if (xhold) xhold[s] = r;      // (one GPU: pos_new itself is the record, DeviceState::xhold)
   vxn[s] = vx[p]; vyn[s] = vy[p]; vzn[s] = vz[p];
   tagn[s] = t;
   imgn[s] = img[p] + dix; imgn[npad + s] = img[npad + p] + diy; imgn[2 * npad + s] = img[2 * npad + p] + diz;
@@ -652,6 +711,15 @@ template <class F> static bool with_build_kernel(const RebuildPlan &p, F &&f) {
 }
 
 void scan_cells(DeviceState &d, int *count, int *start, int nc, int total) {
+  // the four-count kernels move int4: both arrays must start on a 16-byte boundary (blocks of the registry do, a pointer
+  // into the middle of one need not); anything else takes the kernels with one count per thread
+  const bool aligned = (reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(start)) % 16 == 0;
+  if (!d.scan_two_pass && aligned) {
+    const int sb4 = (nc + SCAN_SPAN - 1) / SCAN_SPAN;
+    hipLaunchKernelGGL(k_scan_local4, dim3(sb4), dim3(SCAN_BLOCK), 0, d.stream, nc, count, start, d.scan_tmp);
+    hipLaunchKernelGGL(k_scan_add4, dim3(sb4), dim3(SCAN_BLOCK), 0, d.stream, nc, start, d.scan_tmp, total);
+    return;
+  }
   const int sb = (nc + SCAN_BLOCK - 1) / SCAN_BLOCK;
   hipLaunchKernelGGL(k_scan_local, dim3(sb), dim3(SCAN_BLOCK), 0, d.stream, nc, count, start, d.scan_tmp);
   hipLaunchKernelGGL(k_scan_add, dim3(sb), dim3(SCAN_BLOCK), 0, d.stream, nc, start, d.scan_tmp, total);
@@ -677,7 +745,7 @@ void rebuild_sort(DeviceState &d, const RebuildPlan &plan, int m_in, int n_out, 
                        d.cell_count, d.tag_tmp, d.flags, gone, d.ncells, d.row_tile);
   scan_cells(d, d.cell_count, d.cell_start, nc, m_in);
   d.bins_ready = false;
-  d.cell_count_dirty = false;      // k_scan_local left the counts at zero
+  d.cell_count_dirty = false;      // the scan left the counts at zero
   hipLaunchKernelGGL(k_scatter, dim3(nb), dim3(BLOCK), 0, st, m_in, d.cell_of, d.cell_start, d.tag_tmp, d.perm);
   // one GPU, bonds that need no frozen image: the permute pass also writes the bond-partner table (see k_permute)
   const bool with_bonds = plan.has(RB_PERMUTE_BONDS), phys = plan.has(RB_PERMUTE_PHYS);
@@ -694,11 +762,15 @@ void rebuild_sort(DeviceState &d, const RebuildPlan &plan, int m_in, int n_out, 
   nb = std::max(1, (n + BLOCK - 1) / BLOCK);
   BondTabArgs BT{d.bpa, d.maxtag, d.num_bond, d.bond_type, d.bond_atom, d.bond_pack, d.bond_pack_stride, with_bonds ? d.bpart : (int *)nullptr,
                  nullptr, nullptr, nullptr, 0.0, 0.0, 0.0};
-  hipLaunchKernelGGL(k_permute, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.perm, d.pos, d.pos_tmp, d.xhold, d.v[0],
+  // (xhold_alias: d.pos_tmp is one of the step kernels' pair, never the buffer xhold names - device.h)
+  double4 *const hold_copy = d.xhold_alias ? (double4 *)nullptr : d.pos_hold;
+  hipLaunchKernelGGL(k_permute, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.perm, d.pos, d.pos_tmp, hold_copy, d.v[0],
                      d.v[1], d.v[2], d.v_tmp[0], d.v_tmp[1], d.v_tmp[2], d.tag, d.tag_tmp, d.img, d.img_tmp, d.map, d.posf,
                      plan.has(RB_PREBINNED) ? 1 : 0, d.box, BT, phys ? (const int4 *)d.bond_pack_p[0] : (const int4 *)nullptr, (int4 *)d.bond_pack_p[1], d.flags);
   if (phys) std::swap(d.bond_pack_p[0], d.bond_pack_p[1]);
   std::swap(d.pos, d.pos_tmp);
+  d.xhold = d.xhold_alias ? d.pos : d.pos_hold;      // the build that follows records these positions
+  d.step_rotated = false;
   for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]);
   std::swap(d.tag, d.tag_tmp);
   std::swap(d.img, d.img_tmp);

@@ -24,6 +24,8 @@ struct RebuildKnobs {
   bool no_direct_recv = env_set("LAMMPS_LE_NO_DIRECT_RECV");   // decomposed: halos through the receive buffer + unpack kernel
   long overflow_at = env_set("LAMMPS_LE_TEST_OVERFLOW_AT") ? atol(getenv("LAMMPS_LE_TEST_OVERFLOW_AT")) : -1;   // test hook: shrink the table before this build
   bool freeze_images = env_set("LAMMPS_LE_FREEZE_IMAGES");     // bond partner images frozen at the rebuild even where bond_minimg would hold
+  bool no_xhold_alias = env_set("LAMMPS_LE_NO_XHOLD_ALIAS");   // one GPU: the rebuild stores a copy of the build-time positions (as decomposed runs do)
+  bool scan_two_pass = env_set("LAMMPS_LE_SCAN_TWO_PASS");     // the cell scans with one count per thread (k_scan_local + k_scan_add) instead of four
 };
 
 // What the engine knows when a rebuild starts.
