@@ -810,7 +810,12 @@ double lammps_le_stat(void *handle, const char *name) {
   std::string k = name;
   if (k == "loop_time") return e->loop_time;
   if (k == "neigh_builds") return (double)e->neigh_builds;
-  if (k == "rebuild_plan") return (double)e->rebuild_plan_bits;      // the plan the last rebuild executed: RebuildBit, rebuild_plan.h
+  // the plan the last rebuild executed (RebuildBit, rebuild_plan.h): "rebuild_plan" the bits that follow from the 22 facts of
+  // lammps_le_test_rebuild_plan, i.e. what that hook answers for the same facts; "rebuild_plan_full" with RB_LAZY_V as well
+  if (k == "rebuild_plan") return (double)(e->rebuild_plan_bits & ~(unsigned)RB_LAZY_V);
+  if (k == "rebuild_plan_full") return (double)e->rebuild_plan_bits;
+  if (k == "lazy_rebuilds") return (double)e->lazy_rebuilds;         // rebuilds of the last run under RB_LAZY_V
+  if (k == "velocities_settled") return e->dev ? (double)e->dev->v_settled : 0.0;   // settle_velocities launches since the arrays were allocated
   // time steps of the last run by the path they took: the step kernel (steps_fused_group of them its group variant), its
   // energy variant on a thermo step, the unfused kernels; the three add up to the steps of the run
   if (k == "steps_fused") return (double)e->steps_fused;

@@ -158,6 +158,15 @@ struct DeviceState {
   bool step_rotated = false;                     // the last launch_step rotated three buffers, not two (undo_step_swap)
   float4 *posf = nullptr;                        // FP32 copy of the positions at the last reneighbor (list-build distance test)
   double *v[3] = {nullptr, nullptr, nullptr}, *v_tmp[3] = {nullptr, nullptr, nullptr};
+  // velocities pending: a rebuild under RB_LAZY_V (rebuild_sort) moved every physical array but v.  d.v is then in the order
+  // BEFORE that cell sort and d.perm translates - the bead in slot s has its velocity at v[k][perm[s]] - until the step
+  // kernel that follows hands them over (launch_step: the LAZYV variant reads through perm, stores into v_tmp, the host
+  // swaps).  The state belongs to rebuild_sort (raises it), launch_step (consumes it; undo_step_swap puts it back when the
+  // launch stored nothing) and settle_velocities (permutes v with a kernel of its own).  Whoever else reads or writes d.v
+  // calls settle_velocities first; inside Engine::iterate that never fires.
+  bool v_pending = false;
+  bool step_took_v = false;                      // the last launch_step consumed v_pending (undo_step_swap)
+  long v_settled = 0;                            // launches of settle_velocities (lammps_le_stat("velocities_settled"))
   double *f[3] = {nullptr, nullptr, nullptr};
   int *tag = nullptr, *tag_tmp = nullptr;
   int *img = nullptr, *img_tmp = nullptr;        // [3][npad]
@@ -425,12 +434,18 @@ inline void undo_step_swap(DeviceState &d) {       // the launch stored nothing 
   if (d.step_rotated) std::swap(d.pos_tmp, d.pos_hold);
   std::swap(d.pos, d.pos_tmp);
   d.step_rotated = false;
+  // (the velocities it was to hand over are where they were, perm[] too: the relaunch takes the same arguments)
+  if (d.step_took_v) { for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]); d.v_pending = true; d.step_took_v = false; }
 }
+// d.v in the order of the other physical arrays: a no-op unless a rebuild left the velocities pending (DeviceState::v_pending)
+// and no step kernel has taken them since; then one small kernel on the stream (kernels_neigh.hip)
+void settle_velocities(DeviceState &d);
 // Engine::run, once per `run` command: the mode of this run.  Leaving the alias mode gives xhold its own buffer back.
 void set_xhold_alias(DeviceState &d, bool on);
 inline void note_order_replaced(DeviceState &d) { d.bins_ready = false; d.bond_pack_p_valid = false; }   // the arrays are (about to be) refilled in another order
 inline void note_arrays_allocated(DeviceState &d) {      // dev_alloc: zeroed cell counts, no packed records yet
   note_order_replaced(d);
+  d.v_pending = d.step_took_v = false;
   d.cell_count_dirty = false;
   d.bond_pack_dirty = true;
 }

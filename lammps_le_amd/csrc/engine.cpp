@@ -224,6 +224,7 @@ void Engine::upload() {
     HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, d.stream));
   };
   d.xhold = d.pos_hold;      // (an upload starts the rotation of the position buffers afresh: device.h xhold)
+  settle_velocities(d);
   up(d.pos, pos.data(), np * sizeof(double4));
   up(d.xhold, pos.data(), np * sizeof(double4));
   for (int k = 0; k < 3; k++) {
@@ -398,6 +399,7 @@ void Engine::download() {
     HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, d.stream));
   };
   down(pos.data(), d.pos, np * sizeof(double4));
+  settle_velocities(d);
   for (int k = 0; k < 3; k++) {
     down(vv.data() + (size_t)k * np, d.v[k], np * sizeof(double));
     down(ff.data() + (size_t)k * np, d.f[k], np * sizeof(double));
@@ -471,7 +473,7 @@ static void check_device_error(Engine *e, DeviceState &d) {
 }
 
 // What the engine knows when a rebuild starts (rebuild_plan.h): the one place the flags of DeviceState are read for it
-RebuildFacts Engine::rebuild_facts(bool can_defer, bool sort_due, bool regrow) const {
+RebuildFacts Engine::rebuild_facts(bool can_defer, bool sort_due, bool regrow, bool lazy_v) const {
   const DeviceState &d = *dev;
   RebuildFacts f;
   f.decomposed = d.dd != 0;
@@ -487,6 +489,7 @@ RebuildFacts Engine::rebuild_facts(bool can_defer, bool sort_due, bool regrow) c
   f.snapshot_due = d.le_snapshot && d.topo_dirty;
   f.map_stale = d.map_stale;
   f.sort_due = sort_due; f.can_defer = can_defer; f.regrow = regrow;
+  f.lazy_v = lazy_v && !d.dd;
   f.builds = neigh_builds;
   return f;
 }
@@ -494,10 +497,12 @@ RebuildFacts Engine::rebuild_facts(bool can_defer, bool sort_due, bool regrow) c
 // can_defer: the caller enqueues the step kernel first (it leaves the state untouched if a list overflowed) and then calls
 // finish_reneighbor(); where the plan defers the check, the flags of the build are published but not waited for, and the host
 // round trip of the check (~25 us) is hidden behind that kernel instead of idling the GPU once per rebuild.
-void Engine::reneighbor(bool can_defer, bool sort_due) {
+// lazy_v: that step kernel is the throughput shape of k_step in one launch over every bead - it can take the velocities in
+// the order before this rebuild (rebuild_plan.h RB_LAZY_V)
+void Engine::reneighbor(bool can_defer, bool sort_due, bool lazy_v) {
   DeviceState &d = *dev;
   const double cutneighsq = cutneighmax * cutneighmax;
-  const RebuildPlan plan = plan_rebuild(rebuild_facts(can_defer, sort_due, false), rebuild_knobs);
+  const RebuildPlan plan = plan_rebuild(rebuild_facts(can_defer, sort_due, false, lazy_v), rebuild_knobs);
   rebuild_plan_bits = plan.bits;
   if (plan.has(RB_FORCE_OVERFLOW)) dev_alloc_neigh(d, 4);   // test hook: force an overflow
   // FLAG_MOVED / NEIGH_OVERFLOW / MAXNEIGH are zero here: they are reset by the publish kernel that reports them
@@ -530,6 +535,7 @@ void Engine::reneighbor(bool can_defer, bool sort_due) {
   }
   ago = 0;
   neigh_builds++;
+  if (plan.has(RB_LAZY_V)) lazy_rebuilds++;
   pair_list_ready = true;
 }
 
@@ -991,6 +997,7 @@ void Engine::setup() {
   reneighbor(false, sortfreq > 0);    // pbc + (spatial sort) + Atom::sort + lists; ncalls reset below
   double s1 = wall();
   neigh_builds = 0;
+  lazy_rebuilds = 0;
   steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
@@ -1070,7 +1077,11 @@ void Engine::iterate(long nsteps) {
     if (decide()) {
       const bool sort_due = sortfreq > 0 && ntimestep >= nextsort;
       stamp();
-      reneighbor(plan.fused && !plan.ef, sort_due);     // (a whole fused step follows: the check may wait behind it)
+      // (a whole fused step follows: the check may wait behind it; the throughput shape of the kernel, in one launch, also
+      //  takes the velocities in the old order - the rebuild changes neither the bead count nor the request the shape follows from)
+      const bool lazy_v = plan.fused && plan.next && plan.pair && plan.lpb == 1 && !plan.ahead &&
+                          !plan.ang && !plan.ef && !plan.grp && !plan.diag_bits && !d.dd;
+      reneighbor(plan.fused && !plan.ef, sort_due, lazy_v);
       stamp(T_NEIGH);
     } else {
       stamp();
@@ -1196,6 +1207,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   }
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
+  lazy_rebuilds = 0;
   steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
   for (int l = 0; l <= top; l++) {
     respa_level_forces(l);

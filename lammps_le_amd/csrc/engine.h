@@ -296,12 +296,13 @@ class Engine {
   std::vector<ThermoRow> thermo_log;
   double loop_time = 0.0;
   long neigh_builds = 0, neigh_dangerous = 0;
+  long lazy_rebuilds = 0;      // rebuilds of this run that left the velocities to the step kernel (RB_LAZY_V), lammps_le_stat("lazy_rebuilds")
   // time steps of the current run by the path they took (lammps_le_stat): the step kernel (of which: its group variant), the
   // step kernel's energy variant on a thermo step, the unfused kernels
   long steps_fused = 0, steps_fused_group = 0, steps_fused_thermo = 0, steps_unfused = 0;
   StepKnobs step_knobs;        // the step kernel's environment switches as they stood when the current run began
   RebuildKnobs rebuild_knobs;  // ... and the rebuild's
-  unsigned rebuild_plan_bits = 0;   // the plan the last rebuild (or regrow pass) executed, lammps_le_stat("rebuild_plan")
+  unsigned rebuild_plan_bits = 0;   // the plan the last rebuild (or regrow pass) executed, lammps_le_stat("rebuild_plan_full")
   long rng_late_count = 0;     // decomposed runs: late generations of skipped Langevin stream segments (lammps_le_stat)
   int ago = 0;
   // Timer sections of the loop (src/timer.h:25-28); wall clock between stamps as src/timer.cpp:100-135.  The GPU runs
@@ -427,8 +428,8 @@ class Engine {
   long host_downloads = 0;            // whole-system downloads so far (lammps_le_stat "host_downloads")
   double subset_comm_bytes = 0.0;     // bytes this rank contributed to the collectives of the C-ABI subset calls
   bool timeout_forced = false;        // lammps_force_timeout: runs end at once, as after Timer::force_timeout
-  void reneighbor(bool can_defer = false, bool sort_due = false);   // pbc + spatial sort + cell lists + neighbor list + bond table
-  RebuildFacts rebuild_facts(bool can_defer, bool sort_due, bool regrow) const;   // what plan_rebuild is asked with
+  void reneighbor(bool can_defer = false, bool sort_due = false, bool lazy_v = false);   // pbc + spatial sort + cell lists + neighbor list + bond table
+  RebuildFacts rebuild_facts(bool can_defer, bool sort_due, bool regrow, bool lazy_v = false) const;   // what plan_rebuild is asked with
   bool reneigh_pending = false;       // the build's overflow / error flags are published but not yet looked at
   bool finish_reneighbor();           // waits for them; false = a list overflowed (nothing may depend on the lists yet)
   void regrow_lists();                // grow the table and rebuild until every list fits

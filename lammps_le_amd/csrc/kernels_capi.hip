@@ -109,6 +109,7 @@ static size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
 static void subset_views(DeviceState &d, int prop, int which, const double *&a0, const double *&a1, const double *&a2) {
   a0 = a1 = a2 = nullptr;
   if (prop == SUBSET_V3) {
+    if (which == 0) settle_velocities(d);
     double *const *src = which == 0 ? d.v : d.f;
     a0 = src[0]; a1 = src[1]; a2 = src[2];
   }

@@ -584,6 +584,7 @@ static void swap_counts(DeviceState &d, Comm &comm, int slot_dn, int slot_up) {
 void rebuild_migrate(DeviceState &d, Comm &comm, const RebuildPlan &plan, int &m_in, int &n_out) {
   hipStream_t st = d.stream;
   dd_halo_wait(d);
+  settle_velocities(d);      // (decomposed rebuilds never leave them pending: the migration and the gathers read d.v by slot)
   d.halo_ahead = false;
   d.packed_ahead = false;
   d.packed_peer = 0;       // (a halo the step kernel pushed into the neighbours' windows before a rebuild is never consumed)
@@ -776,6 +777,7 @@ void dd_halo_wait(DeviceState &d) {
 // every rank receives (tag, x, xhold) of all beads: xt / xht by tag for the replicated LE kernels
 void dd_gather_positions(DeviceState &d, Comm &comm) {
   dd_halo_wait(d);
+  settle_velocities(d);
   long maxn = comm.allreduce_host_max(d.n);
   int stride = (int)maxn;
   ensure_gather(d, (size_t)stride * GATH_LE_W, comm.world);
@@ -885,6 +887,7 @@ void dd_gather_needed(DeviceState &d, Comm &comm, int btype, bool with_nbrs) {
 // host download of the whole system: rows of GATH_W doubles for every bead of every rank
 void dd_gather_all(DeviceState &d, Comm &comm, std::vector<double> &rows, int &stride_out) {
   dd_halo_wait(d);
+  settle_velocities(d);
   long maxn = comm.allreduce_host_max(d.n);
   int stride = (int)maxn;
   ensure_gather(d, (size_t)stride * GATH_W, comm.world);

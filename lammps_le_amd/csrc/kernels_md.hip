@@ -598,7 +598,10 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // outside fix nve's group keeps its position and velocity (its force is still computed - others feel it), a bead outside fix
 // langevin's group gets neither drag nor noise and draws nothing; `crank` is then the rank table the draws go by (the rank among
 // the members when the thermostat is on a group)
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP>
+// LAZYV: the first launch after a rebuild that left the velocities in the old order (DeviceState::v_pending) - bead p reads its
+// velocity at vperm[p] and stores it at p of vxo / vyo / vzo: the velocity permutation costs this launch one index per bead
+// instead of the rebuild 48 bytes per bead
+template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV>
 __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
@@ -609,7 +612,9 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
                                           const double4 *__restrict__ xhold, double dtv, double triggersq,
                                           int check, int *__restrict__ flags,
                                           const unsigned char *__restrict__ phase, int which, double (&e)[14], double &ke,
-                                          const int *__restrict__ gmask, int nvebit, int lgbit) {
+                                          const int *__restrict__ gmask, int nvebit, int lgbit,
+                                          const int *__restrict__ vperm, double *__restrict__ vxo,
+                                          double *__restrict__ vyo, double *__restrict__ vzo) {
   int lb = logical_block(A.nblocks);
   const int sub = (LPB == 1) ? 0 : (int)(threadIdx.x % LPB);
   int p = lb * (BLOCK / LPB) + threadIdx.x / LPB;
@@ -619,7 +624,9 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   // check behind this kernel); store nothing, it will rebuild and launch again
   // ---- level 0: all loads addressed by p, issued back to back before any of them is used ----
   double4 ri = A.pos[p];
-  double a = vx[p], b = vy[p], c = vz[p];
+  int pv = p;
+  if (LAZYV) pv = vperm[p];
+  double a = vx[pv], b = vy[pv], c = vz[pv];
   int t = 0;
   if (LANGEVIN || GRP) t = tag[p];
   const BeadPre L = bead_preload<HAS_PAIR, LPB, AHEAD>(A, p, sub);
@@ -722,10 +729,11 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     fx[p] = f0; fy[p] = f1; fz[p] = f2;
   }
   if (DIAG && (A.diag & 64)) { if (a == 1.2345e300) vx[p] = a; return; }   // diagnostic launch: v is left alone (the value is still computed)
-  vx[p] = a; vy[p] = b; vz[p] = c;
+  if (LAZYV) { vxo[p] = a; vyo[p] = b; vzo[p] = c; }
+  else { vx[p] = a; vy[p] = b; vz[p] = c; }
 }
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
-          bool GRP = false>
+          bool GRP = false, bool LAZYV = false>
 __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
                                                 const int *__restrict__ tag, const int *__restrict__ crank,
                                                 const uint32_t *__restrict__ draws, double *__restrict__ vx,
@@ -735,8 +743,13 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
                                                 const double4 *__restrict__ xhold, double dtv, double triggersq,
                                                 int check, int *__restrict__ flags,
                                                 const unsigned char *__restrict__ phase, int which,
-                                                const int *__restrict__ gmask, int nvebit, int lgbit) {
-  // (the three group arguments trail the list: instantiations without GRP never load them, their code is the one it was)
+                                                const int *__restrict__ gmask, int nvebit, int lgbit,
+                                                const int *__restrict__ vperm, double *__restrict__ vxo,
+                                                double *__restrict__ vyo, double *__restrict__ vzo) {
+  // (the three group arguments trail the list: instantiations without GRP never load them, their code is the one it was;
+  //  behind them the four of LAZYV, in the same way)
+  static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
+                "velocity hand-over: the throughput shape only");
   static_assert(!EF || (!NEXT && LPB == 1), "energy variant: NEXT = false, one lane per bead");
   static_assert(!GRP || (!IDENT && !EF && !AHEAD && LPB == 1), "group variant: plain shape, ranks from a table");
   __shared__ double s_tab[6 * (MAXTYPES + 1) * (MAXTYPES + 1)];
@@ -751,9 +764,9 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP>(A, bt, box, tt, s_tab, s_bt, tag, crank, draws, vx, vy, vz, fx, fy, fz,
-                                                                             pos_next, xhold, dtv, triggersq, check, flags, phase, which, e, kev[0],
-                                                                             gmask, nvebit, lgbit);
+  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV>(A, bt, box, tt, s_tab, s_bt, tag, crank, draws, vx, vy, vz, fx, fy, fz,
+                                                                                    pos_next, xhold, dtv, triggersq, check, flags, phase, which, e, kev[0],
+                                                                                    gmask, nvebit, lgbit, vperm, vxo, vyo, vzo);
   if (EF) {
     const int lb = logical_block(A.nblocks);
     if (lb < A.nblocks) {
@@ -768,12 +781,14 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 void launch_initial_integrate(DeviceState &d, const TypeTables &tt, double dtv, double triggersq, bool check, int groupbit) {
   int nb = (d.n + BLOCK - 1) / BLOCK;
   note_positions_replaced(d);     // the positions move
+  settle_velocities(d);
   hipLaunchKernelGGL(k_initial_integrate, dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.v[0], d.v[1], d.v[2],
                      d.f[0], d.f[1], d.f[2], d.xhold, tt, dtv, triggersq, check ? 1 : 0, d.flags, d.tag,
                      groupbit != 1 ? d.gmask : (const int *)nullptr, groupbit);
 }
 void launch_final_integrate(DeviceState &d, const TypeTables &tt, int groupbit) {
   int nb = (d.n + BLOCK - 1) / BLOCK;
+  settle_velocities(d);
   hipLaunchKernelGGL(k_final_integrate, dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.v[0], d.v[1], d.v[2],
                      d.f[0], d.f[1], d.f[2], tt, d.tag, groupbit != 1 ? d.gmask : (const int *)nullptr, groupbit);
 }
@@ -849,6 +864,7 @@ void launch_langevin(DeviceState &d, const TypeTables &tt, bool ident, bool fuse
   const int *gm = groupbit != 1 ? d.gmask : (const int *)nullptr;
   const int *rk = groupbit != 1 ? d.lgrank : d.crank;       // rank among the members of the group
   if (groupbit != 1) ident = false;
+  settle_velocities(d);
   with_flags([&](auto F, auto I) {
     hipLaunchKernelGGL((k_langevin<F, I>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, rk,
                        d.rng_out, d.v[0], d.v[1], d.v[2], d.f[0], d.f[1], d.f[2], tt, gm, groupbit);
@@ -887,6 +903,7 @@ __global__ __launch_bounds__(BLOCK) void k_ke_tensor(int n, const double4 *__res
 }
 void ke_tensor(DeviceState &d, const TypeTables &tt, double *out6) {
   const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  settle_velocities(d);
   hipLaunchKernelGGL(k_ke_tensor, dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.v[0], d.v[1], d.v[2], tt, d.lgsum);
   hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, d.lgsum, d.lgsum + (size_t)nb * 16);
   HIP_CHECK(hipMemcpyAsync(d.partial_h, d.lgsum + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
@@ -895,6 +912,7 @@ void ke_tensor(DeviceState &d, const TypeTables &tt, double *out6) {
 }
 void launch_ke(DeviceState &d, const TypeTables &tt) {
   int nb = (d.n + BLOCK - 1) / BLOCK;
+  settle_velocities(d);
   hipLaunchKernelGGL(k_ke, dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.v[0], d.v[1], d.v[2], tt, d.partial);
 }
 static ForceArgs force_args(DeviceState &d, const double sl[4]) {
@@ -942,7 +960,9 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
   }, eflag, (parts & 1) != 0, parts == 1);
 }
 // The instantiations of k_step that exist (what step_plan.h plans with; implies the two static_asserts inside k_step):
-constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP) {
+constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
+                                   bool LAZYV = false) {
+  if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
   if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
   if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
   if (EF) return !N && P && LPB == 1 && !AHEAD && !ANG;      // thermo step in one pass: L, I = 4
@@ -951,20 +971,24 @@ constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool
 }
 constexpr int count_step_variants() {
   int c = 0;
-  for (int m = 0; m < 1024; m++)
-    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512);
+  for (int m = 0; m < 2048; m++)
+    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024);
   return c;
 }
-static_assert(count_step_variants() == 77, "the set of k_step instantiations changed");
-// f(k_step<the plan's ten template arguments>); false: there is no such instantiation
+static_assert(count_step_variants() == 81, "the set of k_step instantiations changed");
+// f(k_step<the plan's ten template arguments, lazy_v>); false: there is no such instantiation
 template <class F>
-static bool with_step_kernel(const StepPlan &p, F &&f) {
+static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
-  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R) {
+  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z) {
     constexpr int W = W4 ? 4 : 1;
-    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R)) { f(k_step<L, N, I, P, W, D, H, G, E, R>); found = true; }
-  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp);
+    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z>); found = true; }
+  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v);
   return found;
+}
+// the shape that takes velocities a rebuild left pending (Engine::reneighbor states the same as RebuildFacts::lazy_v)
+static bool step_takes_pending_v(const StepPlan &p) {
+  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true) && p.which < 0;
 }
 // ev_start / ev_stop (sampled launches only) take the kernel's own begin / end timestamps from its dispatch packet,
 // the same clock rocprofv3 --kernel-trace reports
@@ -983,12 +1007,18 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
   double4 *pos_next = p.ef ? reinterpret_cast<double4 *>(d.partial) : d.pos_tmp;
   const int *ranks = p.member_ranks ? d.lgrank : d.crank, *gmask = p.grp ? d.gmask : nullptr;
   const int grid = xcd_grid(A.nblocks);
-  const bool found = p.fused && with_step_kernel(p, [&](auto kernel) {
+  // velocities a rebuild left in the old order: this launch hands them over if it is the shape that can, else they are
+  // permuted first.  (a launch that stores nothing - a list overflowed - is undone as a whole: undo_step_swap)
+  const bool lazy_v = d.v_pending && step_takes_pending_v(p);
+  if (!lazy_v) settle_velocities(d);
+  const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel) {
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, d.tag, ranks,
                           d.rng_out, d.v[0], d.v[1], d.v[2], pf0, pf1, pf2, pos_next, d.xhold, a.dtv, a.triggersq, p.check ? 1 : 0,
-                          d.flags, d.phase, p.which, gmask, p.nvebit, p.lgbit);
+                          d.flags, d.phase, p.which, gmask, p.nvebit, p.lgbit, d.perm, d.v_tmp[0], d.v_tmp[1], d.v_tmp[2]);
   });
   if (!found) throw LammpsError("internal: the step plan names a variant of the step kernel that does not exist");
+  d.step_took_v = lazy_v;
+  if (lazy_v) { for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]); d.v_pending = false; }
 }
 void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
   ForceArgs A = force_args(d, a.special_lj);
@@ -1037,7 +1067,7 @@ extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int 
   r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
   r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10];
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
-  const bool known = p.fused && with_step_kernel(p, [](auto) {});
+  const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
   const int v[16] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
                      p.diag_bits, (int)p.lds_pad, known};
   for (int k = 0; k < 16; k++) out[k] = v[k];

@@ -261,11 +261,20 @@ __global__ __launch_bounds__(BLOCK) void k_permute(int n, int npad, const int *_
   if (wrap) wrap_into_box(r, box, dix, diy, diz);   // the step kernel binned these positions: Domain::pbc is applied here
   pos_new[s] = r;
   if (xhold) xhold[s] = r;      // (one GPU: pos_new itself is the record, DeviceState::xhold)
-  vxn[s] = vx[p]; vyn[s] = vy[p]; vzn[s] = vz[p];
+  if (vxn) { vxn[s] = vx[p]; vyn[s] = vy[p]; vzn[s] = vz[p]; }     // (nullptr: RB_LAZY_V, the step kernel moves them)
   tagn[s] = t;
   imgn[s] = img[p] + dix; imgn[npad + s] = img[npad + p] + diy; imgn[2 * npad + s] = img[2 * npad + p] + diz;
   if (!B.bpart) map[t] = s;
   posf[s] = make_float4((float)r.x, (float)r.y, (float)r.z, 0.f);
+}
+// the velocities alone, for whoever needs them in the current order before a step kernel took them (settle_velocities)
+__global__ __launch_bounds__(BLOCK) void k_permute_v(int n, const int *__restrict__ perm, const double *__restrict__ vx,
+                                                     const double *__restrict__ vy, const double *__restrict__ vz,
+                                                     double *__restrict__ vxn, double *__restrict__ vyn, double *__restrict__ vzn) {
+  int s = blockIdx.x * BLOCK + threadIdx.x;
+  if (s >= n) return;
+  const int p = perm[s];
+  vxn[s] = vx[p]; vyn[s] = vy[p]; vzn[s] = vz[p];
 }
 // packed bond records by tag (see DeviceState::bond_pack); run when the bond tables changed
 __global__ __launch_bounds__(BLOCK) void k_bond_pack(int maxtag, int bpa, int stride, const int *__restrict__ num_bond,
@@ -732,7 +741,16 @@ static void bond_pack(DeviceState &d) {
 // sort stage: wrap the owned beads, sort them into cell order (ties by ID), permute the physical arrays.
 // Decomposed runs pass m_in = slots to bin (kept + gone + arrived; their cell, arrival order and counts are in place - the
 // migration stage) and `gone`; n_out beads remain afterwards.
+void settle_velocities(DeviceState &d) {
+  if (!d.v_pending) return;
+  hipLaunchKernelGGL(k_permute_v, dim3(std::max(1, (d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, d.stream, d.n, d.perm, d.v[0], d.v[1], d.v[2],
+                     d.v_tmp[0], d.v_tmp[1], d.v_tmp[2]);
+  for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]);
+  d.v_pending = d.step_took_v = false;
+  d.v_settled++;
+}
 void rebuild_sort(DeviceState &d, const RebuildPlan &plan, int m_in, int n_out, const int *gone) {
+  settle_velocities(d);      // (perm[] is about to be rewritten)
   int nb = std::max(1, (m_in + BLOCK - 1) / BLOCK);
   const int nc = d.ncells + (gone ? 1 : 0);     // + sentinel cell
   hipStream_t st = d.stream;
@@ -764,14 +782,16 @@ void rebuild_sort(DeviceState &d, const RebuildPlan &plan, int m_in, int n_out, 
                  nullptr, nullptr, nullptr, 0.0, 0.0, 0.0};
   // (xhold_alias: d.pos_tmp is one of the step kernels' pair, never the buffer xhold names - device.h)
   double4 *const hold_copy = d.xhold_alias ? (double4 *)nullptr : d.pos_hold;
+  const bool lazy_v = plan.has(RB_LAZY_V);     // the velocities stay in the old order for the step kernel that follows
   hipLaunchKernelGGL(k_permute, dim3(nb), dim3(BLOCK), 0, st, n, d.npad, d.perm, d.pos, d.pos_tmp, hold_copy, d.v[0],
-                     d.v[1], d.v[2], d.v_tmp[0], d.v_tmp[1], d.v_tmp[2], d.tag, d.tag_tmp, d.img, d.img_tmp, d.map, d.posf,
+                     d.v[1], d.v[2], lazy_v ? (double *)nullptr : d.v_tmp[0], d.v_tmp[1], d.v_tmp[2], d.tag, d.tag_tmp, d.img, d.img_tmp, d.map, d.posf,
                      plan.has(RB_PREBINNED) ? 1 : 0, d.box, BT, phys ? (const int4 *)d.bond_pack_p[0] : (const int4 *)nullptr, (int4 *)d.bond_pack_p[1], d.flags);
   if (phys) std::swap(d.bond_pack_p[0], d.bond_pack_p[1]);
   std::swap(d.pos, d.pos_tmp);
   d.xhold = d.xhold_alias ? d.pos : d.pos_hold;      // the build that follows records these positions
   d.step_rotated = false;
-  for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]);
+  if (lazy_v) d.v_pending = true;
+  else for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]);
   std::swap(d.tag, d.tag_tmp);
   std::swap(d.img, d.img_tmp);
   d.n = n_out;
@@ -838,16 +858,26 @@ void rebuild_lists(DeviceState &d, const RebuildPlan &plan, double cutneighsq) {
 // bond_minimg, bpa, bond_pack_stride, bpart, pair, sf1, sf2, sf3, special_asym, row_tile, angles, snapshot_due, map_stale,
 // sort_due, can_defer, regrow, builds; out = the plan's bits, diag_bits, and whether the build dispatcher holds the
 // instantiation the plan names (its own look-up, nothing is launched; 0 for a plan without a build)
-extern "C" void lammps_le_test_rebuild_plan(const int *facts, int *out) {
+static RebuildFacts hook_facts(const int *facts) {
   RebuildFacts f;
   f.decomposed = facts[0]; f.bins_ready = facts[1]; f.counts_dirty = facts[2]; f.bonds_dirty = facts[3]; f.phys_valid = facts[4];
   f.bond_minimg = facts[5]; f.bpa = facts[6]; f.bond_pack_stride = facts[7]; f.bpart = facts[8]; f.pair = facts[9];
   f.sf[1] = facts[10]; f.sf[2] = facts[11]; f.sf[3] = facts[12]; f.special_asym = facts[13]; f.row_tile = facts[14];
   f.angles = facts[15]; f.snapshot_due = facts[16]; f.map_stale = facts[17]; f.sort_due = facts[18]; f.can_defer = facts[19];
   f.regrow = facts[20]; f.builds = facts[21];
+  return f;
+}
+extern "C" void lammps_le_test_rebuild_plan(const int *facts, int *out) {
+  const RebuildFacts f = hook_facts(facts);
   const RebuildPlan p = plan_rebuild(f, RebuildKnobs());
   out[0] = (int)p.bits; out[1] = p.diag_bits;
   out[2] = p.has(RB_BUILD) && with_build_kernel(p, [](auto, auto) {});
+}
+// the same with the 23rd fact, lazy_v, behind the 22 of lammps_le_test_rebuild_plan; out[0] = the plan's bits
+extern "C" void lammps_le_test_rebuild_plan_lazy(const int *facts, int *out) {
+  RebuildFacts f = hook_facts(facts);
+  f.lazy_v = facts[22];
+  out[0] = (int)plan_rebuild(f, RebuildKnobs()).bits;
 }
 
 }  // namespace lmp_le

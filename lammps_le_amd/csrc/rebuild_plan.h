@@ -26,6 +26,7 @@ struct RebuildKnobs {
   bool freeze_images = env_set("LAMMPS_LE_FREEZE_IMAGES");     // bond partner images frozen at the rebuild even where bond_minimg would hold
   bool no_xhold_alias = env_set("LAMMPS_LE_NO_XHOLD_ALIAS");   // one GPU: the rebuild stores a copy of the build-time positions (as decomposed runs do)
   bool scan_two_pass = env_set("LAMMPS_LE_SCAN_TWO_PASS");     // the cell scans with one count per thread (k_scan_local + k_scan_add) instead of four
+  bool permute_all = env_set("LAMMPS_LE_PERMUTE_ALL");         // k_permute moves the velocities at every rebuild (no hand-over to the step kernel)
 };
 
 // What the engine knows when a rebuild starts.
@@ -48,10 +49,13 @@ struct RebuildFacts {
   bool sort_due = false;         // an Atom::sort falls on this rebuild
   bool can_defer = false;        // the caller enqueues a whole fused step next and looks at the build's flags behind it
   bool regrow = false;           // a list overflowed: the table grew, the lists stage runs again for the same order
+  bool lazy_v = false;           // the step kernel enqueued next is the throughput shape of k_step, which can take the velocities
+                                 // in the old order (Engine::reneighbor: the step plan of the iteration; one launch, every bead)
   long builds = 0;               // list builds of this run so far
 };
 
-// One bit per conditional launch and per choice; lammps_le_stat("rebuild_plan") returns the bits of the last plan executed.
+// One bit per conditional launch and per choice; lammps_le_stat("rebuild_plan_full") returns the bits of the last plan executed,
+// lammps_le_stat("rebuild_plan") the same without RB_LAZY_V (the bits lammps_le_test_rebuild_plan knows).
 enum RebuildBit : unsigned {
   RB_WRAP_BIN = 1u << 0,          // k_wrap_bin
   RB_COUNT_MEMSET = 1u << 1,      // cell_count zeroed first (bins nobody consumed)
@@ -76,6 +80,8 @@ enum RebuildBit : unsigned {
   RB_CHECK_DEFERRED = 1u << 23,   // flags published, not waited for (else the synchronous check)
   RB_FORCE_OVERFLOW = 1u << 24,   // test hook: the table shrinks to 4 rows before this rebuild
   RB_ATOM_SORT = 1u << 25,        // the Atom::sort emulation between the cell sort and the lists
+  RB_LAZY_V = 1u << 26,           // k_permute leaves the velocities in the old order: the step kernel that follows reads them
+                                  // through perm[] and stores them in the new one (DeviceState::v_pending)
 };
 constexpr int RB_DDCODE_SHIFT = 16;
 
@@ -114,6 +120,8 @@ inline RebuildPlan plan_rebuild(const RebuildFacts &f, const RebuildKnobs &k) {
     set(RB_TOPO_SNAPSHOT, f.snapshot_due);
     // (an Atom::sort changes the order the build stores pairs in and, decomposed, waits for the device anyway)
     set(RB_CHECK_DEFERRED, f.can_defer && !f.sort_due && !f.decomposed);
+    // the velocities stay behind only where that step kernel is certain to come next, on the order this rebuild leaves
+    set(RB_LAZY_V, f.lazy_v && f.can_defer && !f.sort_due && !f.decomposed && !k.permute_all);
   }
   // the lists stage.  A regrow pass re-derives the same table for the same order (a launch of its own: folded into the
   // prologue of the list build it made that kernel 48 us slower to save 16)

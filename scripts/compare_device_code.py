@@ -2,7 +2,10 @@
 (hipcc <the Makefile's CXXFLAGS> --cuda-device-only -c kernels_md.hip -o X.o) per kernel symbol: the same set of names,
 and for each name the same code bytes and the same kernel descriptor.  Symbol order may differ between the builds, so the
 descriptor's entry offset (bytes 16..23: the distance from the descriptor to the code) is left out of the comparison.
-usage: compare_device_code.py BEFORE.o AFTER.o      (no GPU needed; exit status 1 on any difference)"""
+usage: compare_device_code.py [--renamed] BEFORE.o AFTER.o      (no GPU needed; exit status 1 on any difference)
+--renamed: for a change that adds template or kernel arguments to a kernel, which renames every instantiation - a kernel whose
+name is in the first object only passes if some kernel whose name is in the second object only has the same code bytes and
+the same descriptor but for its kernarg size (bytes 8..11).  Kernels in both objects are compared by name as always."""
 import hashlib
 import os
 import re
@@ -36,11 +39,13 @@ def kernels(obj):
         raw = data[soff + addr - saddr: soff + addr - saddr + size]
         if name.endswith(".kd"):
             raw = raw[:16] + raw[24:]
-        out[name] = (size, hashlib.sha256(raw).hexdigest())
+        out[name] = (size, hashlib.sha256(raw).hexdigest(), hashlib.sha256(raw[:8] + raw[12:]).hexdigest() if name.endswith(".kd") else "")
     return out
 
 
-a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+renamed = "--renamed" in sys.argv[1:]
+args = [x for x in sys.argv[1:] if x != "--renamed"]
+a, b = kernels(args[0]), kernels(args[1])
 ka = {n for n in a if n + ".kd" in a}
 kb = {n for n in b if n + ".kd" in b}
 print("kernels: before %d, after %d; k_step: %d / %d" % (len(ka), len(kb), sum("k_step" in n for n in ka), sum("k_step" in n for n in kb)))
@@ -49,4 +54,10 @@ diff = [n for n in sorted(ka & kb) if a[n] != b[n] or a[n + ".kd"] != b[n + ".kd
 print("names compared: %d, differences: %d" % (len(ka & kb), len(diff)), diff[:5])
 other = sorted(n for n in set(a) ^ set(b))
 print("other symbols in one object only:", other[:10])
+if renamed:
+    new = {(b[n][1], b[n + ".kd"][2]) for n in kb - ka}
+    lost = sorted(n for n in ka - kb if (a[n][1], a[n + ".kd"][2]) not in new)
+    print("renamed: %d kernels of the first object only, %d of the second only; of the first, without a twin in code and descriptor: %d"
+          % (len(ka - kb), len(kb - ka), len(lost)), lost[:5])
+    sys.exit(1 if diff or lost else 0)
 sys.exit(1 if diff or ka != kb else 0)
