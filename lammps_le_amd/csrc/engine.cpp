@@ -1249,7 +1249,7 @@ void Engine::respa_recurse(int l, bool last) {
       } else launch_final_integrate(d, ttl, nbits[k]);
     }
     if (l == top)                                                            // post_integrate_respa: outermost level only
-      for (auto &f : fixes) if (f->has_post_integrate) f->post_integrate();
+      for (auto &f : fixes) if (f->has_post_integrate && f->has_post_integrate_respa) f->post_integrate();
     stamp(T_MODIFY);
     if (l == top && decide()) {
       const bool sort_due = sortfreq > 0 && ntimestep >= nextsort;

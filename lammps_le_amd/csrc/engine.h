@@ -105,6 +105,9 @@ struct Fix {
   // which hooks this fix has (src/fix.h:247-273 mask bits)
   bool has_initial_integrate = false, has_post_integrate = false, has_post_force = false,
        has_final_integrate = false;
+  // POST_INTEGRATE_RESPA: set by ex_load / ex_unload and their src/MC parents; fix extrusion's setmask() leaves it out
+  // (fix_extrusion.cpp:166-171), so under run_style respa the reference never calls it - and neither does respa_recurse
+  bool has_post_integrate_respa = true;
   virtual void initial_integrate() {}
   virtual void post_integrate() {}
   virtual void post_force() {}

@@ -98,6 +98,7 @@ FixExtrusion::FixExtrusion(Engine *e, const std::vector<std::string> &arg) {
   e->say("Attention! maxspecial = " + std::to_string(e->maxspecial) + "\n");
   force_reneighbor = true;
   has_post_integrate = true;
+  has_post_integrate_respa = false;      // :166-171
 }
 double FixExtrusion::compute_vector(int n) { return n == 0 ? (double)last_break : 0.0; }   // :1496-1501
 

@@ -1757,13 +1757,17 @@ static int respa_recurse(leo_t *s, int l, int eflag) {              /* Respa::re
   for (int iloop = 0; iloop < s->respa_loop[l]; iloop++) {
     double t0 = now();
     for (int k = 0; k < s->nfix; k++) if (s->fix[k].kind == FIX_NVE) nve_kick(s, &s->fix[k], s->respa_step[l], l == 0);
-    /* post_integrate_respa: the LE fixes act at the outermost level only (fix_extrusion.cpp:1139-1143, fix_ex_load.cpp:1283-1286,
+    /* post_integrate_respa: the LE fixes act at the outermost level only (fix_ex_load.cpp:1283-1286,
        fix_ex_unload.cpp:694-697, MC/fix_bond_create.cpp:1249-1252, MC/fix_bond_break.cpp:693-696:
        `if (ilevel == nlevels_respa-1) post_integrate()`) */
     if (l == top)
       for (int k = 0; k < s->nfix; k++) {
         leo_fix *fx = &s->fix[k];
         if (fx->kind < FIX_EXTRUSION) continue;
+        /* fix extrusion has the hook but its setmask() (fix_extrusion.cpp:166-171) sets POST_INTEGRATE alone, not
+           POST_INTEGRATE_RESPA as ex_load / ex_unload do (fix_ex_load.cpp:203-204, fix_ex_unload.cpp:137-138): Modify never
+           lists it (modify.cpp:226-227), so under run_style respa it never acts (recorded: tests/golden/ref_respa*.npz) */
+        if (fx->kind == FIX_EXTRUSION) continue;
         if (s->ntimestep % fx->nevery - fx->phase) continue;
         if (fire_fix(s, fx)) return 1;
       }

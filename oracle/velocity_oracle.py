@@ -9,8 +9,10 @@ Follows, as algorithm (no code shared with the engine's C++ restatement):
   src/compute_temp.cpp:60-101  temperature with dof = 3N - 3
   src/group.cpp:1018-1062, 1125-1163, 1426-1459, 1583-1625, 1682-1728   xcm, vcm, angmom, inertia, omega
 
-Parity unpinned: the reference holds no golden vector for this command (its logs only show the requested temperature
-back); the generator itself is pinned by Park & Miller's published check value (seed 1 -> 1043618065 after 10000 draws).
+The reference holds no golden vector for this command (its logs only show the requested temperature back); the generator
+itself is pinned by Park & Miller's published check value (seed 1 -> 1043618065 after 10000 draws), and `create ... loop all`
+and `loop local` (uniform, mom yes, rot no) by two recorded runs of the reference binary (tests/golden/ref_velocity_loop_*.npz);
+the other keywords stay unpinned.
 """
 import math
 

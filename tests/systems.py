@@ -412,3 +412,33 @@ pair_modify shift yes
 pair_coeff * * 1.0 1.0 1.12
 timestep 0.005
 """
+
+# the scripts of the LE tests (test_gpu_le.py and the modules that build on it; reference_runs.py)
+LE = """fix 1 all nve
+fix 2 all langevin 1.0 1.0 1.0 904297
+fix loop all extrusion {n1} {neutral} {left} {right} {tp} 2 {lr}
+fix loading all ex_load {nl} 1 1 1.12 2 {lprob} iparam 1 1 jparam 1 1
+fix unloading all ex_unload {nu} 2 {rmax} {uprob}
+thermo 10
+"""
+
+
+def le_script(n1=10, nl=10, nu=10, neutral=1, left=2, right=3, tp=1.0, lr="4", lprob="prob 0.5 684474",
+              uprob="prob 0.3 456456", rmax=0.5):
+    # soft, long FENE for the extruder bond: stepping every few steps (far faster than any physical N1)
+    # must not run into the reference's own "Bad FENE bond" abort
+    base = CHAIN_SCRIPT.replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 5.0 10.0 1.0 1.0")
+    return base + LE.format(n1=n1, nl=nl, nu=nu, neutral=neutral, left=left, right=right, tp=tp, lr=lr,
+                                    lprob=lprob, uprob=uprob, rmax=rmax)
+
+
+def barrier_types(n, seed, frac=0.15):
+    rng = np.random.RandomState(seed)
+    t = np.ones(n, dtype=np.int32)
+    pick = rng.rand(n) < frac
+    t[pick] = rng.randint(2, 5, size=pick.sum())
+    t[0] = t[-1] = 1
+    return t
+
+
+ANGLE_SCRIPT = CHAIN_SCRIPT.replace("atom_style bond", "atom_style molecular").replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 5.0 10.0 1.0 1.0")

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from systems import CHAIN_SCRIPT, lattice_chain, run_oracle, run_product, write_data
+from systems import ANGLE_SCRIPT, CHAIN_SCRIPT, lattice_chain, run_oracle, run_product, write_data
 from test_gpu_le import melted
 
 pytestmark = pytest.mark.gpu
@@ -64,7 +64,6 @@ def semiflexible(n, nchains, seed, steps=400):
     return s
 
 
-ANGLE_SCRIPT = CHAIN_SCRIPT.replace("atom_style bond", "atom_style molecular").replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 5.0 10.0 1.0 1.0")
 
 
 @pytest.mark.parametrize("style,coeffs", [("harmonic", ("angle_coeff 1 3.0 170.0", "angle_coeff 2 1.0 120.0")),

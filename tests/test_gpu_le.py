@@ -6,7 +6,7 @@ absent roadblock type, extruder bonds that straddle a periodic face (double bond
 import numpy as np
 import pytest
 
-from systems import CHAIN_SCRIPT, lattice_chain, run_oracle, run_product
+from systems import CHAIN_SCRIPT, LE, barrier_types, lattice_chain, le_script, run_oracle, run_product  # noqa: F401 (LE, barrier_types: other test modules take them from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -54,33 +54,6 @@ def compare(p, o, fix_ids):
         assert p.extract_fix(fid, 0, 1, 1) == o.fix_vector(fid)[1], fid
     err = np.abs(p.gather("x") - o.x()).max()
     assert err < 1e-7, err
-
-
-LE = """fix 1 all nve
-fix 2 all langevin 1.0 1.0 1.0 904297
-fix loop all extrusion {n1} {neutral} {left} {right} {tp} 2 {lr}
-fix loading all ex_load {nl} 1 1 1.12 2 {lprob} iparam 1 1 jparam 1 1
-fix unloading all ex_unload {nu} 2 {rmax} {uprob}
-thermo 10
-"""
-
-
-def le_script(n1=10, nl=10, nu=10, neutral=1, left=2, right=3, tp=1.0, lr="4", lprob="prob 0.5 684474",
-              uprob="prob 0.3 456456", rmax=0.5):
-    # soft, long FENE for the extruder bond: stepping every few steps (far faster than any physical N1)
-    # must not run into the reference's own "Bad FENE bond" abort
-    base = CHAIN_SCRIPT.replace("bond_coeff 2 30.0 4.0 1.0 1.0", "bond_coeff 2 5.0 10.0 1.0 1.0")
-    return base + LE.format(n1=n1, nl=nl, nu=nu, neutral=neutral, left=left, right=right, tp=tp, lr=lr,
-                                    lprob=lprob, uprob=uprob, rmax=rmax)
-
-
-def barrier_types(n, seed, frac=0.15):
-    rng = np.random.RandomState(seed)
-    t = np.ones(n, dtype=np.int32)
-    pick = rng.rand(n) < frac
-    t[pick] = rng.randint(2, 5, size=pick.sum())
-    t[0] = t[-1] = 1
-    return t
 
 
 @pytest.mark.parametrize("tp", [1.0, 0.5, 0.0])
@@ -343,7 +316,9 @@ RESPA_STYLES = ["run_style respa 1", "run_style respa 2 4", "run_style respa 3 2
 @pytest.mark.parametrize("style", RESPA_STYLES)
 def test_le_cycle_under_respa(tmp_path, style):
     """extrusion + ex_load + ex_unload with the r-RESPA integrator (bond forces on the inner level by default): topology,
-    special lists and fix counters bit-exact against the oracle's restatement of Respa::recurse, positions to 1e-9."""
+    special lists and fix counters bit-exact against the oracle's restatement of Respa::recurse, positions to 1e-9.  Under
+    any respa, `respa 1` included, fix extrusion stays idle as in the reference (no POST_INTEGRATE_RESPA in its mask,
+    oracle/AUDIT.md R1; recorded: tests/golden/ref_respa2.npz, ref_respa3.npz): ex_load and ex_unload alone edit the bonds."""
     n = 3000
     s = melted(n, types=barrier_types(n, 5))
     script = le_script(tp=0.5) + style + "\nrun 44\n"
@@ -352,14 +327,18 @@ def test_le_cycle_under_respa(tmp_path, style):
     compare(p, o, ("loop", "loading", "unloading"))
     assert len([b for b in o.bond_set() if b[0] == 2]) > 5
     assert p.stat("neigh_builds") == o.neigh_builds()
+    assert o.fix_vector("loop")[0] == 0 and p.extract_fix("loop", 0, 1, 0) == 0 and o.fix_vector("loading")[1] > 0
 
 
 def test_one_level_respa_is_verlet(tmp_path):
     """`run_style respa 1` performs exactly the operations of run_style verlet in the same order (the single level both
-    moves x and carries every force): the two runs agree to the last bit, in the oracle and in the product."""
+    moves x and carries every force): the two runs agree to the last bit, in the oracle and in the product.  Without fix
+    extrusion: its mask has no POST_INTEGRATE_RESPA (fix_extrusion.cpp:166-171), under any respa it never acts, so a script
+    with it is not the verlet run (recorded: tests/golden/ref_respa2.npz; oracle/AUDIT.md R1)."""
     n = 3000
     s = melted(n, types=barrier_types(n, 5))
-    base = le_script(tp=0.5)
+    base = "\n".join(ln for ln in le_script(tp=0.5).split("\n") if not ln.startswith("fix loop "))
+    assert "fix loading" in base and "fix loop" not in base
     ov, orr = run_oracle(base + "run 30\n", s), run_oracle(base + "run_style respa 1\nrun 30\n", s)
     assert np.array_equal(ov.x(), orr.x()) and ov.bond_set() == orr.bond_set()
     pv, pr = run_product(base + "run 30\n", s, tmp_path), run_product(base + "run_style respa 1\nrun 30\n", s, tmp_path)
