@@ -156,9 +156,12 @@ void *lammps_extract_fix(void *handle, char *id, int style, int type, int nrow, 
   BEGIN_CAPTURE
     Fix *f = e->find_fix(id);
     if (!f) throw LammpsError(std::string("Could not find fix ID ") + id);
-    if (style != 0 || type != 1) throw LammpsError("MI355X engine: only global fix vectors can be extracted");
+    const bool scalar = style == 0 && type == 0 && dynamic_cast<FixWallRegion *>(f);      // (the one fix with a global scalar)
+    if (!scalar && (style != 0 || type != 1)) throw LammpsError("MI355X engine: only global fix vectors can be extracted");
+    if (!scalar && f->size_vector() >= 0 && (nrow < 0 || nrow >= f->size_vector()))
+      throw LammpsError("MI355X engine: fix vector is accessed out-of-range");
     double *d = (double *)malloc(sizeof(double));
-    *d = f->compute_vector(nrow);
+    *d = scalar ? f->compute_scalar() : f->compute_vector(nrow);
     result = d;
   END_CAPTURE
   return result;
@@ -646,7 +649,7 @@ static const std::vector<std::pair<std::string, std::vector<std::string>>> &styl
       {"bond", {"fene", "harmonic", "hybrid", "none", "zero"}},
       {"compute", {"pair/local", "property/local"}},
       {"dump", {"atom", "custom", "dcd", "local"}},
-      {"fix", {"bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve"}},
+      {"fix", {"bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve", "wall/region"}},
       {"pair", {"lj/cut", "none", "zero"}},
   };
   return t;
@@ -822,6 +825,7 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "steps_fused_group") return (double)e->steps_fused_group;
   if (k == "steps_fused_thermo") return (double)e->steps_fused_thermo;
   if (k == "steps_unfused") return (double)e->steps_unfused;
+  if (k == "steps_fused_wall") return (double)e->steps_fused_wall;      // of steps_fused: fix wall/region inside the step kernel
   if (k == "neigh_time" || k == "time_neigh") return e->timers[Engine::T_NEIGH];
   if (k == "time_pair") return e->timers[Engine::T_PAIR];
   if (k == "time_bond") return e->timers[Engine::T_BOND];

@@ -51,7 +51,7 @@ constexpr int FLAG_SEQ_SLOT = 32;   // the publish sequence number in the mapped
 enum DevErr {
   ERR_NONE = 0, ERR_BAD_FENE = 1, ERR_BOND_MISSING = 2, ERR_EXT_MULTI = 3, ERR_BPA = 4,
   ERR_SPECIAL = 5, ERR_COUNT_MISMATCH = 6, ERR_NONFINITE = 7, ERR_SPECIAL_SCRATCH = 8, ERR_GHOST_ORDER = 9,
-  ERR_HALO_TIMEOUT = 10, ERR_ANGLES = 11
+  ERR_HALO_TIMEOUT = 10, ERR_ANGLES = 11, ERR_WALL_OUTSIDE = 12
 };
 
 // z-slab decomposition: may `world` ranks share a box `prd_z` tall?  w = prd_z / world is a slab's width, cutghost =
@@ -293,6 +293,8 @@ struct DeviceState {
   int *gmask = nullptr;                                 // [maxtag+2] group bits by tag (bit 0 = all); only when a fix or a local compute acts on a group
                                                         // (uploaded with the system; refreshed in place by Engine::pair_rows for a compute defined since)
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
+  WallTable *walltab_dev = nullptr;                     // fix wall/region: this run's table (k_wall, the wall variant of k_step)
+  double *wall_partial = nullptr;                       // [WALL_MAX][nred_blocks + 1][16] block sums of k_wall<EFLAG> + their totals
   char *angtab_dev = nullptr;                           // AngleTable in device memory (fused angle step)
   bool ghost_whole_shell = false;                       // every bead within the ghost cutoff of a face is sent (runs with an angle style)
   bool map_stale = true;                                // map[] was not left by a decomposed rebuild: fill it before the next one
@@ -402,6 +404,11 @@ void launch_angle(DeviceState &d, const AngleTable &at, bool eflag, bool overwri
 void launch_angle_list(DeviceState &d);       // at every reneighbor of a run with an angle style
 void upload_angle_table(DeviceState &d, const AngleTable &at);   // before the first fused step of a run with an angle style
 void reduce_angle_partials(DeviceState &d, double *out8);
+// fix wall/region (kernels_md.hip): the table of a run; the walls of one place among the post-force fixes added to f (eflag:
+// with the ten block sums per wall); those sums on the host, rows of 16 per wall of the table (synchronises the stream)
+void upload_wall_table(DeviceState &d, const WallTable &wt);
+void launch_wall(DeviceState &d, const WallTable &wt, int phase, bool eflag);
+void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out);
 // reductions: returns sums of `partial` columns on the host (synchronises the stream)
 void reduce_partials(DeviceState &d, double *out16);
 

@@ -465,6 +465,7 @@ static void check_device_error(Engine *e, DeviceState &d) {
     case ERR_NONFINITE: msg = "Non-numeric atom coords - simulation unstable"; break;
     case ERR_HALO_TIMEOUT: msg = "a neighbouring rank did not deliver its halo in time (peer window exchange)"; break;
     case ERR_SPECIAL_SCRATCH: msg = "Special list size exceeded in fix bond/create"; break;
+    case ERR_WALL_OUTSIDE: msg = "Particle outside surface of region used in fix wall/region"; break;
     case ERR_ANGLES: msg = "Fix ex_load induced too many angles/dihedrals/impropers per atom"; break;
     case ERR_GHOST_ORDER: msg = "internal: a ghost's place in the cell order lies outside the block of the neighbour that sent it"; break;
   }
@@ -840,13 +841,54 @@ static void langevin_post_force(Engine *e, FixLangevin *lg, bool fuse_final) {
   rng_langevin_consumed(*e->dev);
 }
 
+// fix wall/region: the table of this run, in fix order; a wall defined behind fix langevin acts behind it (the reference runs
+// the post_force hooks in the order the fixes were defined, src/modify.cpp:463-466)
+void Engine::build_wall_table() {
+  walltab = WallTable{};
+  wall_fixes.clear();
+  bool behind = false;
+  for (auto &f : fixes) {
+    if (dynamic_cast<FixLangevin *>(f.get())) behind = true;
+    auto *w = dynamic_cast<FixWallRegion *>(f.get());
+    if (!w) continue;
+    WallEntry e = w->entry();
+    e.after_langevin = behind ? 1 : 0;
+    walltab.w[walltab.n++] = e;
+    wall_fixes.push_back(w);
+  }
+}
+void Engine::wall_post_force(int phase, bool eflag) {
+  if (walltab.n) launch_wall(*dev, walltab, phase, eflag);
+}
+static int walls_request(const Engine *e) {      // StepRequest::walls
+  if (!e->walltab.n) return 0;
+  for (int k = 0; k < e->walltab.n; k++) if (e->walltab.w[k].groupbit != 1) return 2;
+  return 1;
+}
+static bool walls_behind_langevin(const Engine *e) {
+  for (int k = 0; k < e->walltab.n; k++) if (e->walltab.w[k].after_langevin) return true;
+  return false;
+}
+
 ThermoRow Engine::eval_thermo(bool ke_summed) {
   DeviceState &d = *dev;
   TypeTables tt = make_tables(this, nullptr);
   if (!ke_summed) launch_ke(d, tt);       // (the energy variant of the step kernel has summed the kinetic energy as well)
-  double s[16];
+  // behind the sixteen sums of the force kernel: the ten of every wall (rows of 16), in the same all-reduce
+  double s[16 + 16 * WALL_MAX];
   reduce_partials(d, s);
-  if (world > 1) comm->allreduce_host_sum(s, 16);
+  const int nwall = walltab.n;
+  if (nwall) reduce_wall_partials(d, walltab, s + 16);
+  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * nwall);
+  double efix = 0.0, vfix[6] = {0, 0, 0, 0, 0, 0};      // Modify::thermo_energy (src/compute_pe.cpp:102), the fixes of compute_pressure.cpp:201-220
+  for (int k = 0; k < nwall; k++) {
+    FixWallRegion *w = wall_fixes[k];
+    const double *ws = s + 16 + 16 * k;
+    for (int c = 0; c < 4; c++) w->ewall[c] = ws[c];
+    for (int c = 0; c < 6; c++) w->virial[c] = ws[4 + c];
+    if (w->thermo_energy) efix += w->ewall[0];
+    if (w->thermo_virial) for (int c = 0; c < 6; c++) vfix[c] += w->virial[c];
+  }
   ThermoRow r{};
   r.step = ntimestep;
   double dof = 3.0 * natoms - 3.0;                       // src/compute_temp.cpp:60-68
@@ -863,13 +905,14 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
     r.eangle = a8[0];
     for (int k = 0; k < 6; k++) r.virial[k] += a8[1 + k];
   }
+  for (int k = 0; k < 6; k++) r.virial[k] += vfix[k];
   double vol = box.prd[0] * box.prd[1] * box.prd[2];
   r.press = (dof * boltz * r.temp + r.virial[0] + r.virial[1] + r.virial[2]) / 3.0 / vol * nktv2p;
   const double emol = r.ebond + r.eangle;
   r.epair = r.evdwl / norm; r.emol = emol / norm;
-  r.pe = (r.evdwl + emol) / norm;
+  r.pe = (r.evdwl + emol + efix) / norm;
   r.ke = ke / norm;
-  r.etotal = (ke + r.evdwl + emol) / norm;
+  r.etotal = (ke + r.evdwl + emol + efix) / norm;
   r.nbonds = nbonds;
   if (want_ptensor) {          // (ke_tensor[i] + virial[i]) / volume * nktv2p, src/compute_pressure.cpp:244-290
     double k6[6];
@@ -931,7 +974,13 @@ bool Engine::thermo_keyword(const ThermoRow &r, const std::string &k, double &va
     Fix *f = find_fix(id);
     if (!f) throw LammpsError("Could not find thermo fix ID " + id);
     int idx = (b == std::string::npos) ? 1 : atoi(k.c_str() + b + 1);
-    val = f->compute_vector(idx - 1);
+    if (b == std::string::npos) val = f->compute_scalar();
+    else {
+      if (f->size_vector() >= 0 && (idx < 1 || idx > f->size_vector()))      // src/thermo.cpp:947-949
+        throw LammpsError("Thermo fix vector is accessed out-of-range");
+      val = f->compute_vector(idx - 1);
+    }
+    if (thermo_norm && f->extensive()) val /= norm;      // src/thermo.cpp compute_fix: extensive values per atom under `norm yes`
   }
   else return false;
   return true;
@@ -998,11 +1047,13 @@ void Engine::setup() {
   double s1 = wall();
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = 0;
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
+  wall_post_force(0, true);                       // FixWallRegion::setup -> post_force (src/fix_wall_region.cpp:200-209), in fix order
   if (lg) langevin_post_force(this, lg, false);   // FixLangevin::setup -> post_force (:372-373)
+  wall_post_force(1, true);
   double s2 = wall();
   last_thermo = eval_thermo();
   double s3 = wall();
@@ -1040,6 +1091,7 @@ void Engine::iterate(long nsteps) {
   StepRequest rq;
   rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_lj; rq.angles = ang;
   rq.nvebit = fusable ? nbits[0] : 1; rq.lgbit = lg ? lg->groupbit : 1;
+  rq.walls = walls_request(this);
   bool pre_integrated = false;
   // halo/compute overlap issues the per-step halo on a second stream.  With RCCL that means two streams feeding ONE
   // communicator (ordered by events, but never run on multi-GPU hardware): kept to the test transports unless
@@ -1080,7 +1132,7 @@ void Engine::iterate(long nsteps) {
       // (a whole fused step follows: the check may wait behind it; the throughput shape of the kernel, in one launch, also
       //  takes the velocities in the old order - the rebuild changes neither the bead count nor the request the shape follows from)
       const bool lazy_v = plan.fused && plan.next && plan.pair && plan.lpb == 1 && !plan.ahead &&
-                          !plan.ang && !plan.ef && !plan.grp && !plan.diag_bits && !d.dd;
+                          !plan.ang && !plan.ef && !plan.grp && !plan.wall && !plan.diag_bits && !d.dd;
       reneighbor(plan.fused && !plan.ef, sort_due, lazy_v);
       stamp(T_NEIGH);
     } else {
@@ -1137,6 +1189,7 @@ void Engine::iterate(long nsteps) {
       pre_integrated = next;
       steps_fused++;
       if (plan.grp) steps_fused_group++;
+      if (plan.wall) steps_fused_wall++;
       stamp(T_PAIR);          // the fused kernel: pair + bond + post_force + final_integrate (+ next initial_integrate)
     } else if (plan.fused) {
       // a thermo step without dumps: the step kernel's energy variant - forces, energies, virial, post_force and
@@ -1160,8 +1213,12 @@ void Engine::iterate(long nsteps) {
       steps_unfused++;
       stamp(T_PAIR);          // k_force: pair + bond in one pass
       // (Langevin and the final half-kick in one kernel only when both fixes act on the same atoms)
-      const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag;
+      // fix wall/region at its place among the post-force fixes: before fix langevin, or behind it (no fused half-kick then)
+      wall_post_force(0, eflag);
+      const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag &&
+                                  !walls_behind_langevin(this);
       if (lg) langevin_post_force(this, lg, lg_fused_final);
+      wall_post_force(1, eflag);
       if (!lg_fused_final)
         for (int k = 0; k < nnve; k++) launch_final_integrate(d, tt, nbits[k]);
       pre_integrated = false;
@@ -1208,16 +1265,18 @@ void Engine::respa_setup() {                                   // Respa::setup (
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = 0;
   for (int l = 0; l <= top; l++) {
     respa_level_forces(l);
     launch_flevel_copy(d, d.respa_flevel[l], true, false);
   }
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
-  if (lg) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array
-    launch_flevel_copy(d, d.respa_flevel[top], false, false);
-    langevin_post_force(this, lg, false);
+  if (lg || walltab.n) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
+    launch_flevel_copy(d, d.respa_flevel[top], false, false);     // FixWallRegion::setup likewise (ilevel_respa = the outermost)
+    wall_post_force(0, true);
+    if (lg) langevin_post_force(this, lg, false);
+    wall_post_force(1, true);
     launch_flevel_copy(d, d.respa_flevel[top], true, false);
   }
   compute_forces(true);              // energies and virial of the initial state for the thermo line (forces are reloaded per level)
@@ -1268,7 +1327,12 @@ void Engine::respa_recurse(int l, bool last) {
     stamp();
     respa_level_forces(l);
     stamp(T_PAIR);
-    if (l == top && lg) langevin_post_force(this, lg, false);                // post_force_respa (src/fix_langevin.cpp:576-579)
+    // post_force_respa at the outermost level (src/fix_langevin.cpp:576-579, src/fix_wall_region.cpp:306-309), in fix order; a
+    // thermo step also takes the walls' sums (the positions are the step's last)
+    const bool wall_eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0);
+    if (l == top) wall_post_force(0, wall_eflag);
+    if (l == top && lg) langevin_post_force(this, lg, false);
+    if (l == top) wall_post_force(1, wall_eflag);
     for (int k = 0; k < nnve; k++) launch_final_integrate(d, ttl, nbits[k]); // final_integrate_respa (src/fix_nve.cpp:159-163)
     stamp(T_MODIFY);
   }
@@ -1353,6 +1417,10 @@ void Engine::run(long nsteps) {
   if (dev && dev_current && group_sig != group_signature()) { download(); dev_current = false; }
   if (!dev_current || !dev || !dev->pos) upload();
   group_sig = group_signature();
+  build_wall_table();
+  // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
+  //  region ends every rank - the error flag travels with the displacement test's reduction, Engine::decide)
+  if (walltab.n) upload_wall_table(*dev, walltab);
   if (dev->dd) dd_fast_halo_switch(*dev);
   for (int k = 1; k <= 3; k++) dev->sflag[k] = special_flag(k);
   set_xhold_alias(*dev, !dev->dd && !rebuild_knobs.no_xhold_alias);

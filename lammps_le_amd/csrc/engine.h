@@ -39,6 +39,7 @@ constexpr int NN_NBOND_MASK = 0xFF;          // bond entries of the word: (word 
 // two bits per dimension and bond slot in DeviceState::bshift (0 none, 1 partner at +prd, 2 partner at -prd)
 constexpr int NN_SHIFTED_BIT = 1 << 30;
 constexpr int BSHIFT_BITS = 6;
+constexpr int WALL_MAX = 4;        // fix wall/region instances one run can hold (WallTable)
 
 // ---------------------------------------------------------------------------------------------
 // RanMars in exact integer arithmetic (src/random_mars.cpp:29-95; every value is k * 2^-24)
@@ -86,6 +87,24 @@ struct AngleTable {  // by-value kernel argument: angle_style harmonic | cosine 
   double k[MAXTYPES + 1], theta0[MAXTYPES + 1];   // theta0 in radians
 };
 
+// fix wall/region (src/fix_wall_region.cpp): what the kernels need of every wall, built on the host at every `run`
+enum WallStyle { WALL_LJ93 = 0, WALL_LJ126 = 1, WALL_LJ1043 = 2, WALL_HARMONIC = 3, WALL_MORSE = 4 };
+enum WallRegionKind { WALL_BLOCK = 0, WALL_SPHERE = 1, WALL_CYLINDER = 2 };
+struct WallEntry {
+  int kind, interior, axis;   // region: WallRegionKind, side in (1) | out (0), the cylinder's axis (0 x, 1 y, 2 z)
+  int style;                  // WallStyle
+  int groupbit;               // the fix's group (1 = all)
+  int after_langevin;         // the fix is defined behind fix langevin: its force is added after drag and noise
+  double p[6];                // the region's parameters, as Engine::Region::p
+  double coeff[8];            // coeff1 .. coeff7 of FixWallRegion::init at [1] .. [7]
+  double offset, cutoff;
+  double epsilon, sigma, alpha;   // harmonic: epsilon; morse: D0 (epsilon), r0 (sigma), alpha
+};
+struct WallTable {
+  int n;
+  WallEntry w[WALL_MAX];
+};
+
 struct DeviceState;  // defined in device.h (HIP side)
 struct Comm;         // defined in comm.h
 
@@ -113,6 +132,9 @@ struct Fix {
   virtual void post_force() {}
   virtual void final_integrate() {}
   virtual double compute_vector(int) { throw LammpsError("Fix does not compute a vector"); }
+  virtual double compute_scalar() { return compute_vector(0); }     // `f_ID` without an index
+  virtual int size_vector() const { return -1; }                     // length of the global vector (-1: not checked)
+  virtual bool extensive() const { return false; }                   // extscalar / extvector: thermo divides by the atom count under `norm yes`
 };
 
 struct FixNVE : Fix {
@@ -175,6 +197,24 @@ struct FixExUnload : Fix {   // also the stock `bond/break` (src/MC/fix_bond_bre
   FixExUnload(Engine *e, const std::vector<std::string> &arg);
   void post_integrate() override;
   double compute_vector(int n) override;
+};
+
+// fix ID group wall/region region-ID style args cutoff (src/fix_wall_region.cpp).  The force lives in kernels_md.hip
+// (wall_force); this object holds the script's numbers and the sums of the last evaluation
+struct FixWallRegion : Fix {
+  std::string idregion;
+  int wstyle = WALL_LJ126;
+  double epsilon = 0.0, sigma = 0.0, alpha = 0.0, cutoff = 0.0;
+  bool thermo_energy = false, thermo_virial = false;     // fix_modify energy / virial (src/fix.cpp:63-64: both off)
+  double ewall[4] = {0, 0, 0, 0};                        // energy and the force on the wall, of the last thermo evaluation
+  double virial[6] = {0, 0, 0, 0, 0, 0};                 // xx yy zz xy xz yz
+  FixWallRegion(Engine *e, const std::vector<std::string> &arg);
+  void init() override;                                  // the region may have been deleted since the command
+  WallEntry entry() const;                               // coefficients by the expressions of FixWallRegion::init
+  double compute_scalar() override { return ewall[0]; }
+  double compute_vector(int n) override { return ewall[n + 1]; }
+  int size_vector() const override { return 3; }
+  bool extensive() const override { return true; }       // (src/fix_wall_region.cpp:45-46)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -303,6 +343,12 @@ class Engine {
   // time steps of the current run by the path they took (lammps_le_stat): the step kernel (of which: its group variant), the
   // step kernel's energy variant on a thermo step, the unfused kernels
   long steps_fused = 0, steps_fused_group = 0, steps_fused_thermo = 0, steps_unfused = 0;
+  long steps_fused_wall = 0;   // of steps_fused: the step kernel's wall variant (fix wall/region inside the kernel)
+  // fix wall/region: the table of this run's walls (fix order), the fixes behind its rows
+  WallTable walltab{};
+  std::vector<FixWallRegion *> wall_fixes;
+  void build_wall_table();            // at every run (init() has checked the regions); emptied when the set of fixes changes
+  void wall_post_force(int phase, bool eflag);   // k_wall for the walls before (0) / behind (1) fix langevin
   StepKnobs step_knobs;        // the step kernel's environment switches as they stood when the current run began
   RebuildKnobs rebuild_knobs;  // ... and the rebuild's
   unsigned rebuild_plan_bits = 0;   // the plan the last rebuild (or regrow pass) executed, lammps_le_stat("rebuild_plan_full")

@@ -1,6 +1,7 @@
 // fixes.cpp — fix styles of the hot path, registered under the reference's style names
 // (src/fix_nve.h, src/fix_langevin.h, src/USER-LE/fix_extrusion.h:14-18, fix_ex_load.h, fix_ex_unload.h).
 // Argument grammars and error strings follow the reference constructors.
+#include <cmath>
 #include <cstring>
 
 #include "comm.h"
@@ -69,6 +70,94 @@ FixLangevin::FixLangevin(Engine *e, const std::vector<std::string> &arg) {
   }
   rng.seed(seed);   // seed + comm->me, me = 0
   has_post_force = true;
+}
+
+// fix ID group wall/region region-ID style args cutoff  (src/fix_wall_region.cpp:35-92): lj93 | lj126 | lj1043 | harmonic take
+// epsilon sigma cutoff, morse takes D0 alpha r0 cutoff
+FixWallRegion::FixWallRegion(Engine *e, const std::vector<std::string> &arg) {
+  eng = e; id = arg[0]; group = arg[1]; style = arg[2];
+  const char *ill = "Illegal fix wall/region command";
+  if (arg.size() < 8) throw LammpsError(ill);
+  groupbit = fix_group(e, arg);
+  idregion = arg[3];
+  auto it = e->regions.find(idregion);
+  if (it == e->regions.end()) throw LammpsError("Region ID for fix wall/region does not exist");
+  bool colloid = false;
+  if (arg[4] == "lj93") wstyle = WALL_LJ93;
+  else if (arg[4] == "lj126") wstyle = WALL_LJ126;
+  else if (arg[4] == "lj1043") wstyle = WALL_LJ1043;
+  else if (arg[4] == "colloid") colloid = true;
+  else if (arg[4] == "harmonic") wstyle = WALL_HARMONIC;
+  else if (arg[4] == "morse") wstyle = WALL_MORSE;
+  else throw LammpsError(ill);
+  if (wstyle == WALL_MORSE && !colloid) {
+    if (arg.size() != 9) throw LammpsError(ill);
+    epsilon = numeric(arg[5]); alpha = numeric(arg[6]); sigma = numeric(arg[7]); cutoff = numeric(arg[8]);
+  } else {
+    if (arg.size() != 8) throw LammpsError(ill);
+    epsilon = numeric(arg[5]); sigma = numeric(arg[6]); cutoff = numeric(arg[7]);
+  }
+  if (cutoff <= 0.0) throw LammpsError("Fix wall/region cutoff <= 0.0");
+  // (the reference says this at init(): no atom style of this engine has a radius, so the command is where it ends)
+  if (colloid) throw LammpsError("Fix wall/region colloid requires atom style sphere");
+  // the contact sets the kernels restate: sphere and block from both sides, cylinder from inside
+  init();
+  has_post_force = true;
+}
+void FixWallRegion::init() {      // :115-121 (a region can be deleted, and defined again, between the command and a run)
+  auto it = eng->regions.find(idregion);
+  if (it == eng->regions.end()) throw LammpsError("Region ID for fix wall/region does not exist");
+  const Engine::Region &r = it->second;
+  if (r.style == "union" || r.style == "intersect" || (r.style == "cylinder" && !r.interior))
+    throw LammpsError("MI355X engine: fix wall/region does not support region style " + r.style +
+                      (r.style == "cylinder" ? " with side out" : ""));
+}
+WallEntry FixWallRegion::entry() const {      // :145-190, expression by expression
+  WallEntry w{};
+  const Engine::Region &r = eng->regions.at(idregion);
+  w.kind = r.style == "block" ? WALL_BLOCK : r.style == "sphere" ? WALL_SPHERE : WALL_CYLINDER;
+  w.interior = r.interior ? 1 : 0;
+  w.axis = r.axis - 'x';
+  for (int k = 0; k < 6; k++) w.p[k] = r.p[k];
+  w.style = wstyle; w.groupbit = groupbit;
+  w.cutoff = cutoff; w.epsilon = epsilon; w.sigma = sigma; w.alpha = alpha;
+  double *c = w.coeff;
+  const double MY_2PI = 6.28318530717958647692;
+  if (wstyle == WALL_LJ93) {
+    c[1] = 6.0 / 5.0 * epsilon * pow(sigma, 9.0);
+    c[2] = 3.0 * epsilon * pow(sigma, 3.0);
+    c[3] = 2.0 / 15.0 * epsilon * pow(sigma, 9.0);
+    c[4] = epsilon * pow(sigma, 3.0);
+    double rinv = 1.0 / cutoff;
+    double r2inv = rinv * rinv;
+    double r4inv = r2inv * r2inv;
+    w.offset = c[3] * r4inv * r4inv * rinv - c[4] * r2inv * rinv;
+  } else if (wstyle == WALL_LJ126) {
+    c[1] = 48.0 * epsilon * pow(sigma, 12.0);
+    c[2] = 24.0 * epsilon * pow(sigma, 6.0);
+    c[3] = 4.0 * epsilon * pow(sigma, 12.0);
+    c[4] = 4.0 * epsilon * pow(sigma, 6.0);
+    double r2inv = 1.0 / (cutoff * cutoff);
+    double r6inv = r2inv * r2inv * r2inv;
+    w.offset = r6inv * (c[3] * r6inv - c[4]);
+  } else if (wstyle == WALL_LJ1043) {
+    c[1] = MY_2PI * 2.0 / 5.0 * epsilon * pow(sigma, 10.0);
+    c[2] = MY_2PI * epsilon * pow(sigma, 4.0);
+    c[3] = MY_2PI * pow(2.0, 1 / 2.0) / 3 * epsilon * pow(sigma, 3.0);
+    c[4] = 0.61 / pow(2.0, 1 / 2.0) * sigma;
+    c[5] = c[1] * 10.0;
+    c[6] = c[2] * 4.0;
+    c[7] = c[3] * 3.0;
+    double rinv = 1.0 / cutoff;
+    double r2inv = rinv * rinv;
+    double r4inv = r2inv * r2inv;
+    w.offset = c[1] * r4inv * r4inv * r2inv - c[2] * r4inv - c[3] * pow(cutoff + c[4], -3.0);
+  } else if (wstyle == WALL_MORSE) {
+    c[1] = 2 * epsilon * alpha;
+    double alpha_dr = -alpha * (cutoff - sigma);
+    w.offset = epsilon * (exp(2.0 * alpha_dr) - 2.0 * exp(alpha_dr));
+  }
+  return w;
 }
 
 // fix ID group extrusion N1 neutral ctcf_left ctcf_right through_prob btype [ctcf_left_right]

@@ -108,9 +108,13 @@ struct Parser {
     if (name.rfind("v_", 0) == 0) return e->variable_value(name.substr(2));
     if (name.rfind("f_", 0) == 0) {
       int idx = 1;
-      if (i < s.size() && s[i] == '[') { size_t k = s.find(']', i); if (k == std::string::npos) bad(); idx = atoi(s.c_str() + i + 1); i = k + 1; }
+      bool indexed = false;
+      if (i < s.size() && s[i] == '[') { size_t k = s.find(']', i); if (k == std::string::npos) bad(); idx = atoi(s.c_str() + i + 1); i = k + 1; indexed = true; }
       Fix *f = e->find_fix(name.substr(2));
       if (!f) throw LammpsError("Invalid fix ID in variable formula");
+      if (!indexed) return f->compute_scalar();
+      if (f->size_vector() >= 0 && (idx < 1 || idx > f->size_vector()))      // src/variable.cpp:1698-1702
+        throw LammpsError("Variable formula fix vector is accessed out-of-range");
       return f->compute_vector(idx - 1);
     }
     ws();
@@ -526,14 +530,40 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     else if (st == "extrusion") f.reset(new FixExtrusion(this, arg));
     else if (st == "ex_load" || st == "bond/create") f.reset(new FixExLoad(this, arg));
     else if (st == "ex_unload" || st == "bond/break") f.reset(new FixExUnload(this, arg));
+    else if (st == "wall/region") {
+      int walls = 0;
+      for (auto &g : fixes) if (dynamic_cast<FixWallRegion *>(g.get())) walls++;
+      f.reset(new FixWallRegion(this, arg));
+      if (walls >= WALL_MAX)
+        throw LammpsError("MI355X engine: at most " + std::to_string(WALL_MAX) + " fix wall/region instances (WALL_MAX in engine.h)");
+    }
     else throw LammpsError("Unknown fix style " + st);
     apply_restart_state(f.get());     // a fix re-specified after read_restart continues its RNG stream (Fix::restart)
     fixes.push_back(std::move(f));
+    walltab.n = 0; wall_fixes.clear();      // (the next run builds the table of its walls)
   } else if (cmd == "unfix") {
     need(1);
     auto it = std::find_if(fixes.begin(), fixes.end(), [&](const std::unique_ptr<Fix> &f) { return f->id == arg[0]; });
     if (it == fixes.end()) throw LammpsError("Could not find fix ID to delete");
     fixes.erase(it);
+    walltab.n = 0; wall_fixes.clear();
+  } else if (cmd == "fix_modify") {
+    // src/modify.cpp:1052-1066 modify_fix, src/fix.cpp:134-176 modify_params: energy / virial for a fix that has them
+    if (arg.size() < 2) throw LammpsError("Illegal fix_modify command");
+    Fix *f = find_fix(arg[0]);
+    if (!f) throw LammpsError("Could not find fix_modify ID");
+    auto *w = dynamic_cast<FixWallRegion *>(f);
+    for (size_t k = 1; k < arg.size(); k += 2) {
+      if (k + 2 > arg.size()) throw LammpsError("Illegal fix_modify command");
+      const std::string &kw = arg[k], &val = arg[k + 1];
+      if (kw == "energy" || kw == "virial") {
+        if (val != "yes" && val != "no") throw LammpsError("Illegal fix_modify command");
+        if (!w) throw LammpsError("Illegal fix_modify command");      // (no other fix here has THERMO_ENERGY / virial_flag)
+        (kw == "energy" ? w->thermo_energy : w->thermo_virial) = val == "yes";
+      } else if (kw == "respa" && w) {
+        throw LammpsError("MI355X engine: fix_modify respa is not supported (fix wall/region acts at the outermost level)");
+      } else throw LammpsError("Illegal fix_modify command");
+    }
   } else if (cmd == "thermo") {
     need(1);
     thermo_every = inumeric(arg[0]);

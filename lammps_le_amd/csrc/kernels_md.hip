@@ -10,6 +10,8 @@
 //   BondFENE::compute / BondHarmonic::compute     src/MOLECULE/bond_fene.cpp:52-128, bond_harmonic.cpp:48-101
 //   FixLangevin::post_force_templated<0,...>      src/fix_langevin.cpp:585-778
 //   Neighbor::check_distance                      src/neighbor.cpp:1962-2014
+//   FixWallRegion::post_force + Region::surface   src/fix_wall_region.cpp:220-302, :353-453, src/region.cpp:138-196,
+//                                                 region_sphere.cpp:152-196, region_block.cpp:213-329, region_cylinder.cpp:287-420
 #include "device.h"
 #include "bin_inl.h"
 #include <hip/hip_ext.h>
@@ -494,6 +496,175 @@ __device__ __forceinline__ void bead_force(const ForceArgs &A, const BondTable &
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// fix wall/region: the force of one wall on one bead (FixWallRegion::post_force for one atom).  Region::match first, then the
+// contacts of the region's surface_interior / surface_exterior in their order - up to six for a block seen from inside, three
+// for a cylinder -, each with fwall and eng of the style at the contact distance and fwall * del / r added to the force.  Plain
+// IEEE arithmetic in the reference's operation order (this file is compiled without contraction; 1.0 / r is a divide).  The
+// stored coordinates are taken as they are, the way the reference reads x[i] between reneighborings.  Every branch on the
+// table is wave-uniform.  `acc` (EFLAG): eng, -fx, -fy, -fz, then fx*delx fy*dely fz*delz fx*dely fx*delz fy*delz.
+// false: the bead does not match the region or sits on its surface (r <= 0) - it contributes nothing there, the caller raises
+// ERR_WALL_OUTSIDE ("Particle outside surface of region used in fix wall/region")
+template <bool EFLAG>
+__device__ __forceinline__ bool wall_force(const double4 &x, const WallEntry &w, double &f0, double &f1, double &f2,
+                                           double *__restrict__ acc) {
+  const double cutoff = w.cutoff;
+  const int kind = w.kind;
+  const bool interior = w.interior != 0;
+  // Region::match = !(inside ^ interior), closed surfaces; what the contacts below need is kept
+  double d1 = 0.0, d2 = 0.0, rr = 0.0;       // sphere: rr = distance from the centre; cylinder: d1, d2, rr in the plane across the axis
+  double xp = x.x, yp = x.y, zp = x.z;       // block from outside: the closest point of the block
+  int nslots = 1;
+  bool inside;
+  if (kind == WALL_SPHERE) {
+    const double delx = x.x - w.p[0], dely = x.y - w.p[1], delz = x.z - w.p[2];
+    rr = sqrt(delx * delx + dely * dely + delz * delz);
+    inside = rr <= w.p[3];
+  } else if (kind == WALL_BLOCK) {
+    inside = x.x >= w.p[0] && x.x <= w.p[1] && x.y >= w.p[2] && x.y <= w.p[3] && x.z >= w.p[4] && x.z <= w.p[5];
+    if (interior) nslots = 6;
+    else {
+      if (x.x < w.p[0]) xp = w.p[0]; else if (x.x > w.p[1]) xp = w.p[1];
+      if (x.y < w.p[2]) yp = w.p[2]; else if (x.y > w.p[3]) yp = w.p[3];
+      if (x.z < w.p[4]) zp = w.p[4]; else if (x.z > w.p[5]) zp = w.p[5];
+    }
+  } else {
+    const int ax = w.axis;
+    const double a = ax == 0 ? x.x : ax == 1 ? x.y : x.z;
+    d1 = (ax == 0 ? x.y : x.x) - w.p[0];
+    d2 = (ax == 2 ? x.y : x.z) - w.p[1];
+    rr = sqrt(d1 * d1 + d2 * d2);
+    inside = rr <= w.p[2] && a >= w.p[3] && a <= w.p[4];
+    nslots = 3;
+  }
+  if (inside != interior) return false;
+  bool ok = true;
+#pragma unroll 1
+  for (int m = 0; m < nslots; m++) {
+    double r, delx = 0.0, dely = 0.0, delz = 0.0;
+    if (kind == WALL_SPHERE) {
+      const double radius = w.p[3];
+      if (interior && rr == 0.0) continue;           // (no contact at the centre)
+      r = interior ? radius - rr : rr - radius;
+      const double s = 1.0 - radius / rr;
+      delx = (x.x - w.p[0]) * s; dely = (x.y - w.p[1]) * s; delz = (x.z - w.p[2]) * s;
+    } else if (kind == WALL_BLOCK && interior) {
+      // faces xlo xhi ylo yhi zlo zhi: delta = the distance, del = +-delta along the face's normal
+      const int dim = m >> 1;
+      const double c = dim == 0 ? x.x : dim == 1 ? x.y : x.z;
+      r = (m & 1) ? w.p[m] - c : c - w.p[m];
+      const double del = (m & 1) ? -r : r;
+      if (dim == 0) delx = del; else if (dim == 1) dely = del; else delz = del;
+    } else if (kind == WALL_BLOCK) {
+      if (x.x <= w.p[0] - cutoff || x.x >= w.p[1] + cutoff || x.y <= w.p[2] - cutoff || x.y >= w.p[3] + cutoff ||
+          x.z <= w.p[4] - cutoff || x.z >= w.p[5] + cutoff) continue;
+      delx = x.x - xp; dely = x.y - yp; delz = x.z - zp;
+      r = sqrt(delx * delx + dely * dely + delz * delz);
+    } else {
+      const int ax = w.axis;
+      if (m == 0) {                                  // the curved surface, then the caps at lo and hi
+        if (!(rr > 0.0)) continue;
+        const double radius = w.p[2];
+        r = radius - rr;
+        const double s = 1.0 - radius / rr;
+        const double e1 = d1 * s, e2 = d2 * s;
+        if (ax == 0) { dely = e1; delz = e2; } else if (ax == 1) { delx = e1; delz = e2; } else { delx = e1; dely = e2; }
+      } else {
+        const double a = ax == 0 ? x.x : ax == 1 ? x.y : x.z;
+        r = m == 1 ? a - w.p[3] : w.p[4] - a;
+        const double del = m == 1 ? r : -r;
+        if (ax == 0) delx = del; else if (ax == 1) dely = del; else delz = del;
+      }
+    }
+    if (!(r < cutoff)) continue;
+    if (r <= 0.0) { ok = false; continue; }          // on the surface: onflag, no force from this contact
+    const double rinv = 1.0 / r;
+    double fwall, eng = 0.0;
+    const int style = w.style;
+    if (style == WALL_LJ126) {
+      const double r2inv = rinv * rinv;
+      const double r6inv = r2inv * r2inv * r2inv;
+      fwall = r6inv * (w.coeff[1] * r6inv - w.coeff[2]) * rinv;
+      if (EFLAG) eng = r6inv * (w.coeff[3] * r6inv - w.coeff[4]) - w.offset;
+    } else if (style == WALL_LJ93) {
+      const double r2inv = rinv * rinv;
+      const double r4inv = r2inv * r2inv;
+      const double r10inv = r4inv * r4inv * r2inv;
+      fwall = w.coeff[1] * r10inv - w.coeff[2] * r4inv;
+      if (EFLAG) eng = w.coeff[3] * r4inv * r4inv * rinv - w.coeff[4] * r2inv * rinv - w.offset;
+    } else if (style == WALL_LJ1043) {
+      const double r2inv = rinv * rinv;
+      const double r4inv = r2inv * r2inv;
+      const double r10inv = r4inv * r4inv * r2inv;
+      fwall = w.coeff[5] * r10inv * rinv - w.coeff[6] * r4inv * rinv - w.coeff[7] * pow(r + w.coeff[4], -4.0);
+      if (EFLAG) eng = w.coeff[1] * r10inv - w.coeff[2] * r4inv - w.coeff[3] * pow(r + w.coeff[4], -3.0) - w.offset;
+    } else if (style == WALL_MORSE) {
+      const double dr = r - w.sigma;
+      const double dexp = exp(-w.alpha * dr);
+      fwall = w.coeff[1] * (dexp * dexp - dexp) / r;
+      if (EFLAG) eng = w.epsilon * (dexp * dexp - 2.0 * dexp) - w.offset;
+    } else {
+      const double dr = cutoff - r;
+      fwall = 2.0 * w.epsilon * dr;
+      if (EFLAG) eng = w.epsilon * dr * dr;
+    }
+    const double fx = fwall * delx * rinv, fy = fwall * dely * rinv, fz = fwall * delz * rinv;
+    f0 += fx; f1 += fy; f2 += fz;
+    if (EFLAG) {
+      acc[0] += eng; acc[1] -= fx; acc[2] -= fy; acc[3] -= fz;
+      acc[4] += fx * delx; acc[5] += fy * dely; acc[6] += fz * delz;
+      acc[7] += fx * dely; acc[8] += fx * delz; acc[9] += fy * delz;
+    }
+  }
+  return ok;
+}
+// the walls of one place among the post-force fixes (`phase`: 0 before fix langevin or without one, 1 behind it) on a bead of
+// group all - what the wall variant of the step kernel runs
+__device__ __forceinline__ void walls_on_bead(const WallTable *__restrict__ wt, int phase, const double4 &x, double &f0, double &f1,
+                                              double &f2, int *__restrict__ flags) {
+  const int nw = wt->n;
+#pragma unroll 1
+  for (int k = 0; k < nw; k++) {
+    const WallEntry &w = wt->w[k];
+    if (w.after_langevin != phase) continue;
+    if (!wall_force<false>(x, w, f0, f1, f2, nullptr)) flags[FLAG_ERROR] = ERR_WALL_OUTSIDE;
+  }
+}
+// the unfused post-force kernel of fix wall/region: the walls of one `phase` added to f for the members of each wall's group;
+// EFLAG: per wall the block sums of the ten columns of wall_force into rows of 16 (k_colsum<16> adds them up)
+constexpr int WALL_COLS = 10;
+template <bool EFLAG>
+__global__ __launch_bounds__(BLOCK) void k_wall(int n, const double4 *__restrict__ pos, const int *__restrict__ tag,
+                                                const int *__restrict__ gmask, const WallTable *__restrict__ wt, int phase,
+                                                double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz,
+                                                double *__restrict__ partial, int rows, int *__restrict__ flags) {
+  const int p = blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = p < n;
+  double4 x = make_double4(0.0, 0.0, 0.0, 0.0);
+  double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+  int gm = 1;
+  if (live) {
+    x = pos[p];
+    f0 = fx[p]; f1 = fy[p]; f2 = fz[p];
+    if (gmask) gm = gmask[tag[p]] | 1;
+  }
+  const int nw = wt->n;
+  for (int k = 0; k < nw; k++) {
+    const WallEntry &w = wt->w[k];
+    if (w.after_langevin != phase) continue;
+    double acc[WALL_COLS];
+#pragma unroll
+    for (int c = 0; c < WALL_COLS; c++) acc[c] = 0.0;
+    if (live && (gm & w.groupbit))
+      if (!wall_force<EFLAG>(x, w, f0, f1, f2, acc)) flags[FLAG_ERROR] = ERR_WALL_OUTSIDE;
+    if (EFLAG) {
+      block_reduce_store<WALL_COLS>(acc, partial + (size_t)k * rows * 16, blockIdx.x, 0);
+      __syncthreads();       // (the next wall reuses the reduction's LDS)
+    }
+  }
+  if (live) { fx[p] = f0; fy[p] = f1; fz[p] = f2; }
+}
+
 // forces only (setup, thermo steps, runs without the standard nve+langevin pair of fixes)
 // NOBOND: the bond entries at the head of the lists are skipped (run_style respa with pair and bond forces on different levels)
 template <bool EFLAG, bool HAS_PAIR, bool NOBOND = false>
@@ -601,7 +772,10 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // LAZYV: the first launch after a rebuild that left the velocities in the old order (DeviceState::v_pending) - bead p reads its
 // velocity at vperm[p] and stores it at p of vxo / vyo / vzo: the velocity permutation costs this launch one index per bead
 // instead of the rebuild 48 bytes per bead
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV>
+// WALL: fix wall/region on group all (wall_force): the walls defined before fix langevin add their force before drag and noise,
+// the ones behind it after - the order the reference's post_force hooks run in; the wall needs nothing but the bead's own
+// position, which is in registers here (four lanes per bead: lane 0, behind the butterfly)
+template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL>
 __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
@@ -614,7 +788,8 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
                                           const unsigned char *__restrict__ phase, int which, double (&e)[14], double &ke,
                                           const int *__restrict__ gmask, int nvebit, int lgbit,
                                           const int *__restrict__ vperm, double *__restrict__ vxo,
-                                          double *__restrict__ vyo, double *__restrict__ vzo) {
+                                          double *__restrict__ vyo, double *__restrict__ vzo,
+                                          const WallTable *__restrict__ wt) {
   int lb = logical_block(A.nblocks);
   const int sub = (LPB == 1) ? 0 : (int)(threadIdx.x % LPB);
   int p = lb * (BLOCK / LPB) + threadIdx.x / LPB;
@@ -661,6 +836,9 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     bead_angles<false>(p, ri, reinterpret_cast<const int *>(fy)[p], reinterpret_cast<const int4 *>(fx), A.npad, A.pos, box, at, f0, f1, f2, acc8);
   }
   const int type = (int)ri.w;
+  // (a bead outside its region raises the error flag here, ahead of the `poisoned` test below: a launch that is discarded and
+  //  repeated after a list overflow reports it one launch early, from the same positions the repeated launch reads)
+  if (WALL) walls_on_bead(wt, 0, ri, f0, f1, f2, flags);
   if (LANGEVIN && (!GRP || m_lg)) {
     double gamma1 = tt.g1[type], gamma2 = tt.g2[type];
     const double inv = 1.0 / 16777216.0;
@@ -673,6 +851,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     f1 += fdrag1 + fran1;
     f2 += fdrag2 + fran2;
   }
+  if (WALL && LANGEVIN) walls_on_bead(wt, 1, ri, f0, f1, f2, flags);
   if (poisoned) return;
   const double dtfm = tt.dtfm[type];
   if (!GRP || m_nve) { a += dtfm * f0; b += dtfm * f1; c += dtfm * f2; }          // final_integrate of this step
@@ -733,7 +912,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   else { vx[p] = a; vy[p] = b; vz[p] = c; }
 }
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
-          bool GRP = false, bool LAZYV = false>
+          bool GRP = false, bool LAZYV = false, bool WALL = false>
 __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
                                                 const int *__restrict__ tag, const int *__restrict__ crank,
                                                 const uint32_t *__restrict__ draws, double *__restrict__ vx,
@@ -745,9 +924,12 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
                                                 const unsigned char *__restrict__ phase, int which,
                                                 const int *__restrict__ gmask, int nvebit, int lgbit,
                                                 const int *__restrict__ vperm, double *__restrict__ vxo,
-                                                double *__restrict__ vyo, double *__restrict__ vzo) {
+                                                double *__restrict__ vyo, double *__restrict__ vzo,
+                                                const WallTable *__restrict__ wt) {
   // (the three group arguments trail the list: instantiations without GRP never load them, their code is the one it was;
-  //  behind them the four of LAZYV, in the same way)
+  //  behind them the four of LAZYV and the wall table of WALL, in the same way)
+  static_assert(!WALL || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD)),
+                "wall variant: the three plain shapes with a pair style");
   static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
                 "velocity hand-over: the throughput shape only");
   static_assert(!EF || (!NEXT && LPB == 1), "energy variant: NEXT = false, one lane per bead");
@@ -764,9 +946,9 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV>(A, bt, box, tt, s_tab, s_bt, tag, crank, draws, vx, vy, vz, fx, fy, fz,
+  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL>(A, bt, box, tt, s_tab, s_bt, tag, crank, draws, vx, vy, vz, fx, fy, fz,
                                                                                     pos_next, xhold, dtv, triggersq, check, flags, phase, which, e, kev[0],
-                                                                                    gmask, nvebit, lgbit, vperm, vxo, vyo, vzo);
+                                                                                    gmask, nvebit, lgbit, vperm, vxo, vyo, vzo, wt);
   if (EF) {
     const int lb = logical_block(A.nblocks);
     if (lb < A.nblocks) {
@@ -961,7 +1143,8 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
 }
 // The instantiations of k_step that exist (what step_plan.h plans with; implies the two static_asserts inside k_step):
 constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
-                                   bool LAZYV = false) {
+                                   bool LAZYV = false, bool WALL = false) {
+  if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region inside the step: L, N, I x three shapes = 24
   if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
   if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
   if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
@@ -971,24 +1154,24 @@ constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool
 }
 constexpr int count_step_variants() {
   int c = 0;
-  for (int m = 0; m < 2048; m++)
-    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024);
+  for (int m = 0; m < 4096; m++)
+    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048);
   return c;
 }
-static_assert(count_step_variants() == 81, "the set of k_step instantiations changed");
-// f(k_step<the plan's ten template arguments, lazy_v>); false: there is no such instantiation
+static_assert(count_step_variants() == 105, "the set of k_step instantiations changed");
+// f(k_step<the plan's eleven template arguments, lazy_v before the last>); false: there is no such instantiation
 template <class F>
 static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
-  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z) {
+  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z, auto WL) {
     constexpr int W = W4 ? 4 : 1;
-    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z>); found = true; }
-  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v);
+    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL>); found = true; }
+  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v, p.wall);
   return found;
 }
 // the shape that takes velocities a rebuild left pending (Engine::reneighbor states the same as RebuildFacts::lazy_v)
 static bool step_takes_pending_v(const StepPlan &p) {
-  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true) && p.which < 0;
+  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall) && p.which < 0;
 }
 // ev_start / ev_stop (sampled launches only) take the kernel's own begin / end timestamps from its dispatch packet,
 // the same clock rocprofv3 --kernel-trace reports
@@ -1002,6 +1185,7 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
     pf0 = reinterpret_cast<double *>(d.eff_rec); pf1 = reinterpret_cast<double *>(d.eff_n); pf2 = reinterpret_cast<double *>(d.angtab_dev);
   }
   if (p.grp && !d.gmask) throw LammpsError("internal: fused step on groups without group masks");
+  if (p.wall && !d.walltab_dev) throw LammpsError("internal: fused wall step without the wall table");
   // a thermo step (EF): block totals of energies and virial through the pos_next argument, which it does not use otherwise.
   // Fixes on groups (GRP): the draws of a thermostat on a group go by the rank among its members
   double4 *pos_next = p.ef ? reinterpret_cast<double4 *>(d.partial) : d.pos_tmp;
@@ -1014,7 +1198,8 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
   const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel) {
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, d.tag, ranks,
                           d.rng_out, d.v[0], d.v[1], d.v[2], pf0, pf1, pf2, pos_next, d.xhold, a.dtv, a.triggersq, p.check ? 1 : 0,
-                          d.flags, d.phase, p.which, gmask, p.nvebit, p.lgbit, d.perm, d.v_tmp[0], d.v_tmp[1], d.v_tmp[2]);
+                          d.flags, d.phase, p.which, gmask, p.nvebit, p.lgbit, d.perm, d.v_tmp[0], d.v_tmp[1], d.v_tmp[2],
+                          p.wall ? d.walltab_dev : (const WallTable *)nullptr);
   });
   if (!found) throw LammpsError("internal: the step plan names a variant of the step kernel that does not exist");
   d.step_took_v = lazy_v;
@@ -1071,6 +1256,19 @@ extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int 
   const int v[16] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
                      p.diag_bits, (int)p.lds_pad, known};
   for (int k = 0; k < 16; k++) out[k] = v[k];
+}
+
+// the same with fix wall/region: req[11] = StepRequest::walls; out[16] = StepPlan::wall, out[17] = the plan takes velocities a
+// rebuild left pending (what Engine::iterate asks before it lets a rebuild leave them)
+extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, const int *req, int *out) {
+  StepRequest r;
+  r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
+  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = req[11];
+  const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
+  const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
+  const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
+                     p.diag_bits, (int)p.lds_pad, known, p.wall, step_takes_pending_v(p) && !p.diag_bits && !decomposed};
+  for (int k = 0; k < 18; k++) out[k] = v[k];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1285,6 +1483,38 @@ void reduce_angle_partials(DeviceState &d, double *out8) {
   HIP_CHECK(hipMemcpyAsync(d.partial_h, d.partial_a + (size_t)nb * 8, 8 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
   stream_sync(d);
   for (int k = 0; k < 8; k++) out8[k] = d.partial_h[k];
+}
+
+void upload_wall_table(DeviceState &d, const WallTable &wt) {
+  DEV_RESERVE(d.mem, d.walltab_dev, 1);
+  DEV_RESERVE(d.mem, d.wall_partial, (size_t)WALL_MAX * (d.nred_blocks + 1) * 16);
+  HIP_CHECK(hipMemsetAsync(d.wall_partial, 0, (size_t)WALL_MAX * (d.nred_blocks + 1) * 16 * sizeof(double), d.stream));
+  HIP_CHECK(hipMemcpyAsync(d.walltab_dev, &wt, sizeof(WallTable), hipMemcpyHostToDevice, d.stream));
+  HIP_CHECK(hipStreamSynchronize(d.stream));      // (`wt` is the caller's object)
+}
+void launch_wall(DeviceState &d, const WallTable &wt, int phase, bool eflag) {
+  bool any = false, grouped = false;
+  for (int k = 0; k < wt.n; k++) if (wt.w[k].after_langevin == phase) { any = true; grouped = grouped || wt.w[k].groupbit != 1; }
+  if (!any) return;
+  if (!d.walltab_dev || !d.wall_partial) throw LammpsError("internal: fix wall/region without its table on the device");
+  if (grouped && !d.gmask) throw LammpsError("internal: fix wall/region on a group without group masks");
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  if (nb > d.nred_blocks) throw LammpsError("internal: more blocks than rows of block sums");
+  with_flags([&](auto E) {
+    hipLaunchKernelGGL((k_wall<E>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, grouped ? d.gmask : (const int *)nullptr,
+                       d.walltab_dev, phase, d.f[0], d.f[1], d.f[2], d.wall_partial, d.nred_blocks + 1, d.flags);
+  }, eflag);
+}
+void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out) {
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  const size_t rows = (size_t)d.nred_blocks + 1;
+  for (int k = 0; k < wt.n; k++) {
+    double *tab = d.wall_partial + (size_t)k * rows * 16;
+    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+    HIP_CHECK(hipMemcpyAsync(d.partial_h + 16 * (size_t)k, tab + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+  }
+  stream_sync(d);
+  for (int k = 0; k < 16 * wt.n; k++) out[k] = d.partial_h[k];
 }
 
 // sum the per-block partials in a fixed order (deterministic); the totals land in the table's spare row nb

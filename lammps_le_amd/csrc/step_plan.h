@@ -29,11 +29,13 @@ struct StepKnobs {
 // What the engine knows about the step.  langevin: a fix langevin acts; next: another step follows, its initial_integrate rides
 // along (no forces are stored); ident: the reference's local index of a bead is its ID - 1; pair: a pair style; angles: an
 // angle style is active; thermo: thermo output after this step, energies and virial are wanted; check: the displacement test
-// of Neighbor::check_distance is due; cells: the cell tables the binning writes are allocated
+// of Neighbor::check_distance is due; cells: the cell tables the binning writes are allocated; walls: fix wall/region - 0 none,
+// 1 walls the step kernel can take (every one on group all), 2 walls that force the unfused kernels (one of them on a group)
 struct StepRequest {
   bool langevin = false, next = false, ident = false, pair = false, angles = false, thermo = false, check = false, cells = false;
   int nvebit = 1, lgbit = 1; // group bits of fix nve / fix langevin (1 = all)
   int which = -1;            // decomposed runs with halo / compute overlap: the phase this launch handles (-1: every bead)
+  int walls = 0;
 };
 
 struct StepPlan {
@@ -42,6 +44,7 @@ struct StepPlan {
   bool langevin = false, next = false, ident = false, pair = false;
   int lpb = 1;
   bool diag = false, ahead = false, ang = false, ef = false, grp = false;
+  bool wall = false;         // the twelfth: fix wall/region evaluated inside the kernel (wall_force)
   bool bin = false;          // positions binned by this launch
   bool member_ranks = false; // the draws go by the rank among the members of fix langevin's group, not by the canonical rank
   int diag_bits = 0;         // != 0: the diagnostic launch <true, true, true, true, 1, DIAG> goes first, with these parts switched off
@@ -60,6 +63,12 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   p.langevin = r.langevin; p.next = r.next; p.ident = r.ident; p.pair = r.pair;
   p.which = r.which; p.nvebit = r.nvebit; p.lgbit = r.lgbit; p.check = r.check; p.lds_pad = k.lds_pad;
   p.grp = r.nvebit != 1 || r.lgbit != 1;
+  if (r.walls) {
+    // fix wall/region: the wall variant covers the plain steps of a run whose walls all act on group all, with a pair style, no
+    // angle style and no fix on a group; thermo steps (the wall's energy and virial) and everything else take k_wall
+    if (r.walls != 1 || p.grp || r.thermo || r.angles || !r.pair) return unfused;
+    p.wall = true;
+  }
   if (p.grp) {
     // fix nve / fix langevin on a group: one lane per bead, ranks from a table; with an angle style only the throughput shape
     // (the look-ahead shape of small systems has no group + angle instantiation); thermo steps take the unfused kernels
@@ -82,7 +91,7 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   // positions binned by this launch: single GPU, whole-step launch with a displacement test in it, one lane per bead (with
   // four lanes per bead - small systems - it was measured slower than the separate k_wrap_bin: 62.2k vs 64.5k steps/s at 32k)
   p.bin = p.check && p.next && !decomposed && r.which < 0 && p.lpb != 4 && !k.no_fused_bin && r.cells;
-  if (k.diag_step && r.langevin && r.next && r.ident && r.pair && r.which < 0 && p.lpb != 4 && !p.ef) p.diag_bits = k.diag_step;
+  if (k.diag_step && r.langevin && r.next && r.ident && r.pair && r.which < 0 && p.lpb != 4 && !p.ef && !p.wall) p.diag_bits = k.diag_step;
   return p;
 }
 
