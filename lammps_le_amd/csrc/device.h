@@ -188,7 +188,8 @@ struct DeviceState {
   // the other two hold (copies go out of step when fix ex_unload's influence rule spares one atom).  eff_*[t]: the listed
   // angles bead t is part of, sorted, so that the force kernel is a per-bead gather with a fixed summation order.
   int ecap = 0;
-  int *eff_n = nullptr, *eff_rec = nullptr;      // [npad], int4 [ecap][npad] = (type, i1, i2, i3) with PHYSICAL indices, column-major
+  int *eff_n = nullptr;                          // [npad]
+  int4 *eff_rec = nullptr;                       // [ecap][npad] = (type, i1, i2, i3) with PHYSICAL indices, column-major
   // bond tables as of the last reneighbor = the reference's neighbor->bondlist, which the LE fixes loop over
   // even when another LE fix changed the topology earlier in the same step (fix_ex_unload.cpp:223, fix_extrusion.cpp:368)
   int *num_bond0 = nullptr, *bond_type0 = nullptr, *bond_atom0 = nullptr;
@@ -295,7 +296,7 @@ struct DeviceState {
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
   WallTable *walltab_dev = nullptr;                     // fix wall/region: this run's table (k_wall, the wall variant of k_step)
   double *wall_partial = nullptr;                       // [WALL_MAX][nred_blocks + 1][16] block sums of k_wall<EFLAG> + their totals
-  char *angtab_dev = nullptr;                           // AngleTable in device memory (fused angle step)
+  AngleTable *angtab_dev = nullptr;                     // this run's table in device memory (fused angle step)
   bool ghost_whole_shell = false;                       // every bead within the ghost cutoff of a face is sent (runs with an angle style)
   bool map_stale = true;                                // map[] was not left by a decomposed rebuild: fill it before the next one
   int nsend[2] = {0, 0}, nrecv[2] = {0, 0};

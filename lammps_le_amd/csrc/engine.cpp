@@ -1131,9 +1131,7 @@ void Engine::iterate(long nsteps) {
       stamp();
       // (a whole fused step follows: the check may wait behind it; the throughput shape of the kernel, in one launch, also
       //  takes the velocities in the old order - the rebuild changes neither the bead count nor the request the shape follows from)
-      const bool lazy_v = plan.fused && plan.next && plan.pair && plan.lpb == 1 && !plan.ahead &&
-                          !plan.ang && !plan.ef && !plan.grp && !plan.wall && !plan.diag_bits && !d.dd;
-      reneighbor(plan.fused && !plan.ef, sort_due, lazy_v);
+      reneighbor(plan.fused && !plan.ef, sort_due, takes_pending_v(plan, d.dd != 0));
       stamp(T_NEIGH);
     } else {
       stamp();

@@ -199,6 +199,9 @@ struct ForceArgs {
   int maxrow;            // highest list row a lane may touch before it knows its count: (maxneigh - 1 - sub) / LPB >= this
   int nn_limit;          // diagnostics only (LAMMPS_LE_NN_LIMIT): cap on neighbors visited per bead
   int diag;              // diagnostics only (LAMMPS_LE_DIAG_STEP): extra launch with parts off, see launch_step
+  // ---- from here on read by the step kernel only (k_force carries them unused).  They stay here because the kernel-argument
+  // layout decides which scalar loads the compiler merges: with these members behind the type tables the NEXT wall variants,
+  // which are bound by SGPRs, spill several times as many of them (1 -> 7, 4 -> 19, 7 -> 54) ----
   // a launch that tests the skin/2 displacement (a rebuild may follow) also bins the new positions: cell, arrival order
   // inside the cell and the cell counts, i.e. everything k_wrap_bin would produce except Domain::pbc itself (k_permute)
   const float4 *holdf;   // float copy of xhold (= posf of the last build; nullptr: use xhold only)
@@ -209,6 +212,37 @@ struct ForceArgs {
   // decomposed runs: border beads also write their new position into the halo send buffer (no pack launch per step)
   const int *sendslot;   // (behind its npad words: the {slot below, slot above} pairs of the beads in both lists, DeviceState::sendboth)
   double4 *send_dn, *send_up;   // the staging buffer's two halves, or the neighbours' windows (kernels_dd.hip, fast halo)
+};
+
+// The run-time arguments of the step kernel (k_step) by name, one by-value kernel argument; launch_step_kernel fills it, a
+// member that the launched instantiation does not use is null.  Two things a member of a by-value struct does not get, and what
+// is done about them:
+//  - `noalias`: k_step hands the pointers on to the __restrict__ parameters of step_body, which restores it where the loads
+//    are scheduled;
+//  - an invariant load: a direct kernel argument is loaded where it is used (the load can be rematerialised), a member at the
+//    kernel's entry, and it then holds its SGPRs to the end.  The five pointers the kernel uses last - fx, fy, fz, pos_next,
+//    xhold - are therefore direct arguments of k_step behind this struct: as members they cost the wall variants up to 17
+//    SGPR spills, scratch and, in two of them, the fourth wave.
+struct StepKernelArgs {
+  const int *tag;
+  const int *ranks;      // tag -> rank the draws go by: canonical, or among the members of fix langevin's group (GRP)
+  const uint32_t *draws;
+  double *vx, *vy, *vz;
+  double dtv, triggersq;
+  int check;
+  int *flags;
+  const unsigned char *phase;
+  int which;             // decomposed runs with halo / compute overlap: the phase this launch handles (-1: every bead)
+  const int *gmask;      // GRP: group masks by tag, and the bits of fix nve / fix langevin
+  int nvebit, lgbit;
+  const int *vperm;      // LAZYV: bead p reads its velocity at vperm[p] and stores it at p of vxo / vyo / vzo
+  double *vxo, *vyo, *vzo;
+  const WallTable *walls;   // WALL
+  // ANG && NEXT: the bead's listed angles (k_angle_list), their counts and the coefficient table in device memory
+  const int4 *angle_rec;
+  const int *angle_n;
+  const AngleTable *angles;
+  double *partial;       // EF: block totals of energies and virial, rows of 16 as k_force<EFLAG> writes them
 };
 
 // reciprocal by v_rcp_f64 + two Newton steps (<= 1 ulp from the IEEE quotient 1/x; an IEEE divide is ~35 instructions)
@@ -764,10 +798,10 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // EF: a thermo step - the same pass also sums the energies and the virial of the pair and bond terms into `partial`
 // (rows of 16 per block, as k_force<EFLAG> writes them), so that a step with thermo output is not a pass of k_force
 // plus a Langevin / integrate kernel.  Only for NEXT = false, one lane per bead (the velocities thermo reads are those
-// after final_integrate); the block totals travel in through `pos_next`, which a NEXT = false launch does not use.
+// after final_integrate).
 // GRP: fix nve and / or fix langevin act on a group (`mask[i] & groupbit`, src/fix_nve.cpp:82, src/fix_langevin.cpp:661): a bead
 // outside fix nve's group keeps its position and velocity (its force is still computed - others feel it), a bead outside fix
-// langevin's group gets neither drag nor noise and draws nothing; `crank` is then the rank table the draws go by (the rank among
+// langevin's group gets neither drag nor noise and draws nothing; `ranks` is then the rank table the draws go by (the rank among
 // the members when the thermostat is on a group)
 // LAZYV: the first launch after a rebuild that left the velocities in the old order (DeviceState::v_pending) - bead p reads its
 // velocity at vperm[p] and stores it at p of vxo / vyo / vzo: the velocity permutation costs this launch one index per bead
@@ -775,8 +809,11 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // WALL: fix wall/region on group all (wall_force): the walls defined before fix langevin add their force before drag and noise,
 // the ones behind it after - the order the reference's post_force hooks run in; the wall needs nothing but the bead's own
 // position, which is in registers here (four lanes per bead: lane 0, behind the butterfly)
+// The parameters from `tag` on are the members of S and k_step's five direct pointers once more, __restrict__-qualified: the
+// loads of level 0 / level 1 below and of the AHEAD shapes move ahead of the stores into `flags` only with it (StepKernelArgs).
+// Read straight from S here, the members give 2 instantiations other VGPR counts and the wall variants vector loads of their table.
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL>
-__device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt,
+__device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt, const StepKernelArgs &S,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
                                           const uint32_t *__restrict__ draws, double *__restrict__ vx,
@@ -832,8 +869,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     // whole steps of a run with an angle style evaluate the bead's listed angles right here; a NEXT launch stores no forces,
     // so its three force pointers carry the angle data instead: records, counts, coefficient table (launch_step)
     double acc8[8];
-    const AngleTable &at = *reinterpret_cast<const AngleTable *>(fz);
-    bead_angles<false>(p, ri, reinterpret_cast<const int *>(fy)[p], reinterpret_cast<const int4 *>(fx), A.npad, A.pos, box, at, f0, f1, f2, acc8);
+    bead_angles<false>(p, ri, S.angle_n[p], S.angle_rec, A.npad, A.pos, box, *S.angles, f0, f1, f2, acc8);
   }
   const int type = (int)ri.w;
   // (a bead outside its region raises the error flag here, ahead of the `poisoned` test below: a launch that is discarded and
@@ -914,20 +950,13 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
           bool GRP = false, bool LAZYV = false, bool WALL = false>
 __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
-                                                const int *__restrict__ tag, const int *__restrict__ crank,
-                                                const uint32_t *__restrict__ draws, double *__restrict__ vx,
-                                                double *__restrict__ vy, double *__restrict__ vz,
-                                                double *__restrict__ fx, double *__restrict__ fy,
-                                                double *__restrict__ fz, double4 *__restrict__ pos_next,
-                                                const double4 *__restrict__ xhold, double dtv, double triggersq,
-                                                int check, int *__restrict__ flags,
-                                                const unsigned char *__restrict__ phase, int which,
-                                                const int *__restrict__ gmask, int nvebit, int lgbit,
-                                                const int *__restrict__ vperm, double *__restrict__ vxo,
-                                                double *__restrict__ vyo, double *__restrict__ vzo,
-                                                const WallTable *__restrict__ wt) {
-  // (the three group arguments trail the list: instantiations without GRP never load them, their code is the one it was;
-  //  behind them the four of LAZYV and the wall table of WALL, in the same way)
+                                                                                           StepKernelArgs S, double *__restrict__ fx,
+                                                                                           double *__restrict__ fy, double *__restrict__ fz,
+                                                                                           double4 *__restrict__ pos_next,
+                                                                                           const double4 *__restrict__ xhold) {
+  // (fx, fy, fz: stored by launches without NEXT, read first when ANG && !NEXT; why these five are not members: StepKernelArgs)
+  static_assert(sizeof(ForceArgs) + sizeof(BondTable) + sizeof(Box) + sizeof(TypeTables) + sizeof(StepKernelArgs) <= 4096,
+                "the by-value arguments of k_step exceed the 4 KiB kernel-argument limit");
   static_assert(!WALL || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD)),
                 "wall variant: the three plain shapes with a pair style");
   static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
@@ -946,14 +975,14 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL>(A, bt, box, tt, s_tab, s_bt, tag, crank, draws, vx, vy, vz, fx, fy, fz,
-                                                                                    pos_next, xhold, dtv, triggersq, check, flags, phase, which, e, kev[0],
-                                                                                    gmask, nvebit, lgbit, vperm, vxo, vyo, vzo, wt);
+  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL>(
+      A, bt, box, tt, S, s_tab, s_bt, S.tag, S.ranks, S.draws, S.vx, S.vy, S.vz, fx, fy, fz, pos_next, xhold, S.dtv, S.triggersq, S.check, S.flags,
+      S.phase, S.which, e, kev[0], S.gmask, S.nvebit, S.lgbit, S.vperm, S.vxo, S.vyo, S.vzo, S.walls);
   if (EF) {
     const int lb = logical_block(A.nblocks);
     if (lb < A.nblocks) {
-      block_reduce_store<14>(e, reinterpret_cast<double *>(pos_next), lb, 0);
-      block_reduce_store<1>(kev, reinterpret_cast<double *>(pos_next), lb, 14);
+      block_reduce_store<14>(e, S.partial, lb, 0);
+      block_reduce_store<1>(kev, S.partial, lb, 14);
     }
   }
 }
@@ -1141,25 +1170,7 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
       hipLaunchKernelGGL((k_force<E, P, NOBOND>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
   }, eflag, (parts & 1) != 0, parts == 1);
 }
-// The instantiations of k_step that exist (what step_plan.h plans with; implies the two static_asserts inside k_step):
-constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
-                                   bool LAZYV = false, bool WALL = false) {
-  if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region inside the step: L, N, I x three shapes = 24
-  if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
-  if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
-  if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
-  if (EF) return !N && P && LPB == 1 && !AHEAD && !ANG;      // thermo step in one pass: L, I = 4
-  if (ANG) return P && LPB == 1;                             // angles inside the step: L, N, I, AHEAD = 16
-  return LPB == 1 || AHEAD;                                  // L, N, I, P x {four lanes, one lane ahead, one lane} = 48
-}
-constexpr int count_step_variants() {
-  int c = 0;
-  for (int m = 0; m < 4096; m++)
-    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048);
-  return c;
-}
-static_assert(count_step_variants() == 105, "the set of k_step instantiations changed");
-// f(k_step<the plan's eleven template arguments, lazy_v before the last>); false: there is no such instantiation
+// f(k_step<the plan's eleven template arguments, lazy_v as LAZYV before the last>); false: there is no such instantiation
 template <class F>
 static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
@@ -1169,37 +1180,42 @@ static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v, p.wall);
   return found;
 }
-// the shape that takes velocities a rebuild left pending (Engine::reneighbor states the same as RebuildFacts::lazy_v)
-static bool step_takes_pending_v(const StepPlan &p) {
-  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall) && p.which < 0;
-}
-// ev_start / ev_stop (sampled launches only) take the kernel's own begin / end timestamps from its dispatch packet,
-// the same clock rocprofv3 --kernel-trace reports
+// Fills the kernel's argument record from the device state, the plan and the launch's arguments - the one place that does -
+// and launches the instantiation the plan names.  ev_start / ev_stop (sampled launches only) take the kernel's own begin /
+// end timestamps from its dispatch packet, the same clock rocprofv3 --kernel-trace reports
 static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArgs &A, const StepArgs &a, hipEvent_t ev_start,
                                hipEvent_t ev_stop) {
-  // a whole step of a run with an angle style (NEXT) evaluates the listed angles inside the kernel: records, counts and the
-  // coefficient table travel in the three force pointers, which a NEXT launch does not otherwise use (step_body)
-  double *pf0 = d.f[0], *pf1 = d.f[1], *pf2 = d.f[2];
+  StepKernelArgs S = {};
+  S.tag = d.tag; S.draws = d.rng_out;
+  // fixes on groups (GRP): the draws of a thermostat on a group go by the rank among its members
+  S.ranks = p.member_ranks ? d.lgrank : d.crank;
+  S.vx = d.v[0]; S.vy = d.v[1]; S.vz = d.v[2];
+  S.dtv = a.dtv; S.triggersq = a.triggersq; S.check = p.check ? 1 : 0;
+  S.flags = d.flags; S.phase = d.phase; S.which = p.which;
+  S.nvebit = p.nvebit; S.lgbit = p.lgbit;
+  S.vperm = d.perm; S.vxo = d.v_tmp[0]; S.vyo = d.v_tmp[1]; S.vzo = d.v_tmp[2];
+  if (p.grp) {
+    if (!d.gmask) throw LammpsError("internal: fused step on groups without group masks");
+    S.gmask = d.gmask;
+  }
+  if (p.wall) {
+    if (!d.walltab_dev) throw LammpsError("internal: fused wall step without the wall table");
+    S.walls = d.walltab_dev;
+  }
+  // a whole step of a run with an angle style (NEXT) evaluates the listed angles inside the kernel
   if (p.ang && p.next) {
     if (!d.eff_rec || !d.eff_n || !d.angtab_dev) throw LammpsError("internal: fused angle step without angle records");
-    pf0 = reinterpret_cast<double *>(d.eff_rec); pf1 = reinterpret_cast<double *>(d.eff_n); pf2 = reinterpret_cast<double *>(d.angtab_dev);
+    S.angle_rec = d.eff_rec; S.angle_n = d.eff_n; S.angles = d.angtab_dev;
   }
-  if (p.grp && !d.gmask) throw LammpsError("internal: fused step on groups without group masks");
-  if (p.wall && !d.walltab_dev) throw LammpsError("internal: fused wall step without the wall table");
-  // a thermo step (EF): block totals of energies and virial through the pos_next argument, which it does not use otherwise.
-  // Fixes on groups (GRP): the draws of a thermostat on a group go by the rank among its members
-  double4 *pos_next = p.ef ? reinterpret_cast<double4 *>(d.partial) : d.pos_tmp;
-  const int *ranks = p.member_ranks ? d.lgrank : d.crank, *gmask = p.grp ? d.gmask : nullptr;
+  if (p.ef) S.partial = d.partial;     // a thermo step: block totals of energies and virial
   const int grid = xcd_grid(A.nblocks);
   // velocities a rebuild left in the old order: this launch hands them over if it is the shape that can, else they are
   // permuted first.  (a launch that stores nothing - a list overflowed - is undone as a whole: undo_step_swap)
-  const bool lazy_v = d.v_pending && step_takes_pending_v(p);
+  const bool lazy_v = d.v_pending && takes_pending_v(p, d.dd != 0);
   if (!lazy_v) settle_velocities(d);
   const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel) {
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, d.tag, ranks,
-                          d.rng_out, d.v[0], d.v[1], d.v[2], pf0, pf1, pf2, pos_next, d.xhold, a.dtv, a.triggersq, p.check ? 1 : 0,
-                          d.flags, d.phase, p.which, gmask, p.nvebit, p.lgbit, d.perm, d.v_tmp[0], d.v_tmp[1], d.v_tmp[2],
-                          p.wall ? d.walltab_dev : (const WallTable *)nullptr);
+    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, S,
+                          d.f[0], d.f[1], d.f[2], d.pos_tmp, d.xhold);
   });
   if (!found) throw LammpsError("internal: the step plan names a variant of the step kernel that does not exist");
   d.step_took_v = lazy_v;
@@ -1243,32 +1259,30 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
   launch_step_kernel(d, p, A, a, a.ev_start, a.ev_stop);
   if (p.next && a.swap_buffers) note_step_swapped(d);
 }
-// test hook (not part of the reference surface, not declared in include/lammps_le.h): the plan for a request under the
+// test hooks (not part of the reference surface, not declared in include/lammps_le.h): the plan for a request under the
 // environment switches as they stand at this call.  req = langevin, next, ident, pair, angles, thermo, nvebit, lgbit, which,
-// check, cells; out = fused, the ten template arguments in k_step's order, bin, member_ranks, diag_bits, lds_pad, and whether
-// the dispatcher of launch_step holds the instantiation the plan names (its own look-up, nothing is launched)
-extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
+// check, cells, walls (StepRequest::walls); out = fused, the plan's first ten template arguments in k_step's order (langevin
+// ... grp), bin, member_ranks, diag_bits, lds_pad, whether the dispatcher of launch_step holds the instantiation the plan names
+// (its own look-up, nothing is launched), then [16] = StepPlan::wall and [17] = the plan takes velocities a rebuild left pending
+static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out) {
   StepRequest r;
   r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
-  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10];
-  const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
-  const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
-  const int v[16] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
-                     p.diag_bits, (int)p.lds_pad, known};
-  for (int k = 0; k < 16; k++) out[k] = v[k];
-}
-
-// the same with fix wall/region: req[11] = StepRequest::walls; out[16] = StepPlan::wall, out[17] = the plan takes velocities a
-// rebuild left pending (what Engine::iterate asks before it lets a rebuild leave them)
-extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, const int *req, int *out) {
-  StepRequest r;
-  r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
-  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = req[11];
+  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls;
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
   const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
   const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
-                     p.diag_bits, (int)p.lds_pad, known, p.wall, step_takes_pending_v(p) && !p.diag_bits && !decomposed};
+                     p.diag_bits, (int)p.lds_pad, known, p.wall, takes_pending_v(p, decomposed != 0)};
   for (int k = 0; k < 18; k++) out[k] = v[k];
+}
+// eleven inputs (no walls), the first 16 outputs
+extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
+  int v[18];
+  test_step_plan(n_owned, decomposed, req, 0, v);
+  for (int k = 0; k < 16; k++) out[k] = v[k];
+}
+// twelve inputs, req[11] = walls; all 18 outputs
+extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, const int *req, int *out) {
+  test_step_plan(n_owned, decomposed, req, req[11], out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1421,10 +1435,10 @@ void launch_angle_list(DeviceState &d) {
     d.angle_pack_dirty = false;
   }
   hipLaunchKernelGGL(k_angle_list, dim3(nb), dim3(BLOCK), 0, d.stream, T, d.apa, d.ecap, d.npad, d.ident_order ? (const int *)nullptr : d.crank,
-                     d.map, d.posf, d.box, d.dd ? d.n : -1, d.num_angle, d.angle_type, d.angle_a1, d.angle_a2, d.angle_a3, d.eff_n, (int4 *)d.eff_rec, d.flags,
+                     d.map, d.posf, d.box, d.dd ? d.n : -1, d.num_angle, d.angle_type, d.angle_a1, d.angle_a2, d.angle_a3, d.eff_n, d.eff_rec, d.flags,
                      (const int4 *)d.angle_pack, pack_stride);
   hipLaunchKernelGGL(k_angle_sort, dim3(std::max(1, (d.n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, d.stream, d.n, d.ecap, d.npad, d.eff_n,
-                     (int4 *)d.eff_rec);
+                     d.eff_rec);
 }
 
 template <bool EFLAG, bool OVERWRITE = false>
@@ -1464,7 +1478,7 @@ __global__ __launch_bounds__(BLOCK) void k_angle(int n, int ecap, Box box, Angle
 }
 // the coefficient table in device memory, for the fused step (kernel arguments of k_step are not to be touched)
 void upload_angle_table(DeviceState &d, const AngleTable &at) {
-  DEV_RESERVE(d.mem, d.angtab_dev, sizeof(AngleTable));
+  DEV_RESERVE(d.mem, d.angtab_dev, 1);
   HIP_CHECK(hipMemcpyAsync(d.angtab_dev, &at, sizeof(AngleTable), hipMemcpyHostToDevice, d.stream));
   HIP_CHECK(hipStreamSynchronize(d.stream));      // (`at` is the caller's object)
 }
@@ -1474,7 +1488,7 @@ void launch_angle(DeviceState &d, const AngleTable &at, bool eflag, bool overwri
   with_flags([&](auto E, auto O) {      // (the fused step kernel adds the forces of an `overwrite` launch to its own sums; no energies then)
     if constexpr (!(E && O))
       hipLaunchKernelGGL((k_angle<E, O>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.ecap, d.box, at, d.pos, d.npad, d.eff_n,
-                         (const int4 *)d.eff_rec, d.f[0], d.f[1], d.f[2], d.partial_a, d.flags);
+                         d.eff_rec, d.f[0], d.f[1], d.f[2], d.partial_a, d.flags);
   }, eflag && !overwrite, overwrite);
 }
 void reduce_angle_partials(DeviceState &d, double *out8) {

@@ -1,7 +1,7 @@
 // step_plan.h — which instantiation of the fused step kernel (k_step, kernels_md.hip) a time step takes, or that it takes
 // the unfused kernels.  Plain host code without a device in it: Engine::iterate states what it knows about the step
 // (StepRequest), plan_step answers, launch_step launches what the plan says.  The set of instantiations that exist is
-// step_variant_exists (kernels_md.hip); tests/test_step_plan_cpu.py holds the two against each other.
+// step_variant_exists (below); tests/test_step_plan_cpu.py holds the two against each other.
 #pragma once
 #include <cstdlib>
 
@@ -40,11 +40,11 @@ struct StepRequest {
 
 struct StepPlan {
   bool fused = false;        // false: not covered by the step kernel, take the unfused kernels (nothing below means anything)
-  // the template arguments of k_step
+  // eleven of the twelve template arguments of k_step (the twelfth, LAZYV, is decided at the launch: takes_pending_v)
   bool langevin = false, next = false, ident = false, pair = false;
   int lpb = 1;
   bool diag = false, ahead = false, ang = false, ef = false, grp = false;
-  bool wall = false;         // the twelfth: fix wall/region evaluated inside the kernel (wall_force)
+  bool wall = false;         // fix wall/region evaluated inside the kernel (wall_force)
   bool bin = false;          // positions binned by this launch
   bool member_ranks = false; // the draws go by the rank among the members of fix langevin's group, not by the canonical rank
   int diag_bits = 0;         // != 0: the diagnostic launch <true, true, true, true, 1, DIAG> goes first, with these parts switched off
@@ -93,6 +93,34 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   p.bin = p.check && p.next && !decomposed && r.which < 0 && p.lpb != 4 && !k.no_fused_bin && r.cells;
   if (k.diag_step && r.langevin && r.next && r.ident && r.pair && r.which < 0 && p.lpb != 4 && !p.ef && !p.wall) p.diag_bits = k.diag_step;
   return p;
+}
+
+// The instantiations of k_step that exist, by its twelve template arguments (what plan_step plans with; implies the four
+// static_asserts inside k_step): 24 + 4 + 1 + 8 + 4 + 16 + 48 = 105
+constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
+                                   bool LAZYV = false, bool WALL = false) {
+  if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region inside the step: L, N, I x three shapes = 24
+  if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
+  if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
+  if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
+  if (EF) return !N && P && LPB == 1 && !AHEAD && !ANG;      // thermo step in one pass: L, I = 4
+  if (ANG) return P && LPB == 1;                             // angles inside the step: L, N, I, AHEAD = 16
+  return LPB == 1 || AHEAD;                                  // L, N, I, P x {four lanes, one lane ahead, one lane} = 48
+}
+constexpr int count_step_variants() {
+  int c = 0;
+  for (int m = 0; m < 4096; m++)
+    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048);
+  return c;
+}
+static_assert(count_step_variants() == 105, "the set of k_step instantiations changed");
+
+// The launch of this plan takes the velocities a rebuild left in the old order (DeviceState::v_pending): the throughput shape
+// of the kernel, in one launch over every bead of one GPU, with no diagnostic launch in front of it.  Engine::iterate asks
+// before it lets a rebuild leave them, launch_step when it picks the instantiation.
+inline bool takes_pending_v(const StepPlan &p, bool decomposed) {
+  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall) &&
+         p.which < 0 && !p.diag_bits && !decomposed;
 }
 
 }  // namespace lmp_le

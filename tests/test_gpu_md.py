@@ -122,11 +122,15 @@ def test_velocity_create_between_runs(tmp_path, n):
     {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "1000000000"},  # loads issued ahead
     {"LAMMPS_LE_LPB": "4"},                                          # four lanes per bead
     {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "0", "LAMMPS_LE_NO_FUSED_THERMO": "1"},   # thermo steps through k_force + k_langevin
-], ids=["plain", "ahead", "lpb4", "plain-unfused-thermo"])
+    {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "0", "LAMMPS_LE_DIAG_STEP": "2"},         # the diagnostic launch ahead of every whole step
+], ids=["plain", "ahead", "lpb4", "plain-unfused-thermo", "plain-diag"])
 def test_step_kernel_variants(tmp_path, env):
     """Every variant of the fused step kernel (chosen by system size in production) on the same system: hybrid bonds,
     fractional special weights, two atom types, Langevin; against the oracle.  "plain" takes its thermo steps (every 25th)
-    through the energy variant of the step kernel, as systems above 64k beads do."""
+    through the energy variant of the step kernel, as systems above 64k beads do.  "plain-diag" is "plain" with the diagnostic
+    instantiation launched before every whole step (pair loop off): the system is in identity order (data file in ID order,
+    `atom_modify sort 0 0`), so the plan keeps the pre-launch; it writes only the second position buffer, which the real launch
+    overwrites, so every assertion of "plain" holds unchanged."""
     import pickle
     import subprocess
     import sys
@@ -160,7 +164,7 @@ def test_step_kernel_variants(tmp_path, env):
     assert steps["steps_fused"] > 0
     if "LAMMPS_LE_NO_FUSED_THERMO" in env:
         assert steps["steps_fused_thermo"] == 0
-    elif env == {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "0"}:     # plain: thermo every 25 over 60 steps - 25, 50, 60
+    elif env.get("LAMMPS_LE_LPB") == "1" and env.get("LAMMPS_LE_AHEAD_MAX_N") == "0":     # plain, plain-diag: thermo every 25 over 60 steps - 25, 50, 60
         assert steps["steps_fused_thermo"] == 3
 
 

@@ -35,8 +35,8 @@ def _hook():
 
 
 def expected(n, dd, r, env):
-    """The rules of the step kernel's choice: (ten template arguments of k_step, bin, draws by the member-rank table, bits
-    of the diagnostic pre-launch, LDS pad) or UNFUSED."""
+    """The rules of the step kernel's choice: (the first ten of k_step's twelve template arguments, bin, draws by the
+    member-rank table, bits of the diagnostic pre-launch, LDS pad) or UNFUSED."""
     L, N, I, P, angles, thermo, nvebit, lgbit, which, check, cells = r
     L, N, I, P = bool(L), bool(N), bool(I), bool(P)
     if "LAMMPS_LE_NO_FUSE" in env:
@@ -71,7 +71,10 @@ def expected(n, dd, r, env):
 
 
 def exists(L, N, I, P, LPB, DIAG, AHEAD, ANG, EF, GRP):
-    """The 77 instantiations of k_step: 16 * 3 + 8 * 2 + 4 + 8 + 1."""
+    """The rule of csrc/step_plan.h step_variant_exists, restated for the ten template arguments a request without walls
+    decides (LAZYV and WALL false): 77 of k_step's 105 instantiations - 16 * 3 + 8 * 2 + 4 + 8 + 1.  The other 28 are the
+    four that take the velocities a rebuild left pending (tests/test_lazy_permute_cpu.py) and the 24 of fix wall/region
+    (tests/test_wall_cpu.py)."""
     if DIAG:
         return (L, N, I, P, LPB, AHEAD, ANG, EF, GRP) == (True, True, True, True, 1, False, False, False, False)
     if GRP:
@@ -114,7 +117,8 @@ def test_plan_matches_rules_and_dispatcher(env, monkeypatch):
 
 
 def test_all_variants_reachable_and_switches_reread(monkeypatch):
-    """Every instantiation but the diagnostic one is some plan's answer; the switches are read at the call, not once per process."""
+    """Every instantiation of the ten-argument subset (77) but the diagnostic one is some plan's answer; the switches are read at
+    the call, not once per process."""
     plan = _hook()
     for name in NAMES:
         monkeypatch.delenv(name, raising=False)
