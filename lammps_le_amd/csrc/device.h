@@ -51,8 +51,12 @@ constexpr int FLAG_SEQ_SLOT = 32;   // the publish sequence number in the mapped
 enum DevErr {
   ERR_NONE = 0, ERR_BAD_FENE = 1, ERR_BOND_MISSING = 2, ERR_EXT_MULTI = 3, ERR_BPA = 4,
   ERR_SPECIAL = 5, ERR_COUNT_MISMATCH = 6, ERR_NONFINITE = 7, ERR_SPECIAL_SCRATCH = 8, ERR_GHOST_ORDER = 9,
-  ERR_HALO_TIMEOUT = 10, ERR_ANGLES = 11, ERR_WALL_OUTSIDE = 12
+  ERR_HALO_TIMEOUT = 10, ERR_ANGLES = 11, ERR_WALL_OUTSIDE = 12,
+  ERR_ONE_SIDED = 13     // fix extrusion: the higher end of a new bond has no free slot, the lower end has (kernels_le.hip k_ext_create)
 };
+// The one table code -> text (engine.cpp).  `style`: the fix that was firing when the code was raised - the reference's fixes
+// each carry their own copy of the code that raises, and the copies end their texts in different names.
+std::string device_error_text(int code, const std::string &style);
 
 // z-slab decomposition: may `world` ranks share a box `prd_z` tall?  w = prd_z / world is a slab's width, cutghost =
 // max(neighbor cutoff, comm_modify cutoff) the depth of a ghost shell.  Three conditions, in the order they are tested:

@@ -451,26 +451,34 @@ void Engine::download() {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Texts of the reference.  ERR_SPECIAL_SCRATCH (rebuild_special_one): fix ex_load's copy names ex_load (fix_ex_load.cpp:818,
+// :837); fix extrusion's copy and the stock fix say bond/create (fix_extrusion.cpp:1081, :1101; MC/fix_bond_create.cpp:784,
+// :803); the copies of ex_unload and bond/break do not check, and the engine stops with the stock text there.
+std::string device_error_text(int code, const std::string &style) {
+  const std::string st = style.empty() ? "ex_load" : style;
+  switch (code) {
+    case ERR_BAD_FENE: return "Bad FENE bond";
+    case ERR_BOND_MISSING: return "Bond atoms missing";
+    case ERR_EXT_MULTI: return "Fix extrusion, more than one bond type 2";
+    case ERR_BPA: return "New bond exceeded bonds per atom in fix " + st;
+    case ERR_SPECIAL: return "New bond exceeded special list size in fix " + st;
+    case ERR_COUNT_MISMATCH: return "Numbers of created and broken bonds are not equal";
+    case ERR_NONFINITE: return "Non-numeric atom coords - simulation unstable";
+    case ERR_HALO_TIMEOUT: return "a neighbouring rank did not deliver its halo in time (peer window exchange)";
+    case ERR_SPECIAL_SCRATCH: return std::string("Special list size exceeded in fix ") + (st == "ex_load" ? "ex_load" : "bond/create");
+    case ERR_WALL_OUTSIDE: return "Particle outside surface of region used in fix wall/region";
+    case ERR_ANGLES: return "Fix " + st + " induced too many angles/dihedrals/impropers per atom";
+    case ERR_GHOST_ORDER: return "internal: a ghost's place in the cell order lies outside the block of the neighbour that sent it";
+    // not the reference's: there the run goes on with the bond stored by its lower end alone, which this engine cannot hold
+    // (every bond is evaluated from both ends' own tables)
+    case ERR_ONE_SIDED: return "fix " + st + ": a new bond would be stored by one end only (bonds per atom)";
+  }
+  return "device error";
+}
 static void check_device_error(Engine *e, DeviceState &d) {
   int code = d.flags_h[FLAG_ERROR];
   if (!code) return;
-  const char *msg = "device error";
-  switch (code) {
-    case ERR_BAD_FENE: msg = "Bad FENE bond"; break;
-    case ERR_BOND_MISSING: msg = "Bond atoms missing"; break;
-    case ERR_EXT_MULTI: msg = "Fix extrusion, more than one bond type 2"; break;
-    case ERR_BPA: msg = "New bond exceeded bonds per atom in fix ex_load"; break;
-    case ERR_SPECIAL: msg = "New bond exceeded special list size in fix ex_load"; break;
-    case ERR_COUNT_MISMATCH: msg = "Numbers of created and broken bonds are not equal"; break;
-    case ERR_NONFINITE: msg = "Non-numeric atom coords - simulation unstable"; break;
-    case ERR_HALO_TIMEOUT: msg = "a neighbouring rank did not deliver its halo in time (peer window exchange)"; break;
-    case ERR_SPECIAL_SCRATCH: msg = "Special list size exceeded in fix bond/create"; break;
-    case ERR_WALL_OUTSIDE: msg = "Particle outside surface of region used in fix wall/region"; break;
-    case ERR_ANGLES: msg = "Fix ex_load induced too many angles/dihedrals/impropers per atom"; break;
-    case ERR_GHOST_ORDER: msg = "internal: a ghost's place in the cell order lies outside the block of the neighbour that sent it"; break;
-  }
-  (void)e;
-  throw LammpsError(msg);
+  throw LammpsError(device_error_text(code, e->le_style));
 }
 
 // What the engine knows when a rebuild starts (rebuild_plan.h): the one place the flags of DeviceState are read for it

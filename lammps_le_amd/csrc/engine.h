@@ -485,6 +485,7 @@ class Engine {
   bool decide();                      // Neighbor::decide (src/neighbor.cpp:1933-1948)
   void emulate_atom_sort();           // keep `crank` equal to the reference's local order (Atom::sort)
   std::vector<long> le_reneigh_step;  // next_reneighbor per fix
+  std::string le_style;               // style of the LE fix that fired last (device_error_text)
 
   // ---- output ----
   FILE *screen = stdout, *logfile = nullptr;

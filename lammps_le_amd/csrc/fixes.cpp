@@ -319,19 +319,9 @@ static int le_slot(Engine *e, Fix *f) {
   }
   return s;
 }
-static void check_le_error(DeviceState &d, const char *style) {
+static void check_le_error(DeviceState &d, const std::string &style) {
   int code = d.flags_h[FLAG_ERROR];
-  if (!code) return;
-  std::string st = style;
-  switch (code) {
-    case ERR_EXT_MULTI: throw LammpsError("Fix extrusion, more than one bond type 2");
-    case ERR_BPA: throw LammpsError("New bond exceeded bonds per atom in fix " + st);
-    case ERR_SPECIAL: throw LammpsError("New bond exceeded special list size in fix " + st);
-    case ERR_COUNT_MISMATCH: throw LammpsError("Numbers of created and broken bonds are not equal");
-    case ERR_SPECIAL_SCRATCH: throw LammpsError("Special list size exceeded in fix bond/create");
-    case ERR_ANGLES: throw LammpsError("Fix " + st + " induced too many angles/dihedrals/impropers per atom");
-    default: throw LammpsError("device error in fix " + st);
-  }
+  if (code) throw LammpsError(device_error_text(code, style));
 }
 
 void FixExtrusion::post_integrate() {
@@ -340,6 +330,7 @@ void FixExtrusion::post_integrate() {
   int slot = le_slot(eng, this);
   if (slot >= LE_MAX_FIXES) throw LammpsError("MI355X engine supports at most " + std::to_string(LE_MAX_FIXES) + " extrusion/ex_load/ex_unload fixes");
   if (!rng_on_device) { le_rng_upload(d, slot, rng); rng_on_device = true; }
+  eng->le_style = style;
   if (eng->world > 1) {
     // stored coordinates of the extruder ends and the beads they can step to: O(extruders) rows (dd_gather_needed); every
     // bead's (tag, x, xhold) only when the visit order is not the canonical one
@@ -349,10 +340,15 @@ void FixExtrusion::post_integrate() {
   launch_extrusion(d, p, slot);
   note_topology_changed(d);
   sync_flags(d);
-  check_le_error(d, "extrusion");
+  // the reference's order: the bondcount pass and the insert of a new bond stop it inside their loops (:292, :764), then the
+  // two counts are compared (:808), and only then update_topology rebuilds special rows (:1081).  A bond that its higher end
+  // cannot store leaves the counts equal and the reference running (ERR_ONE_SIDED: this engine stops)
+  const int code = d.flags_h[FLAG_ERROR];
+  if (code == ERR_EXT_MULTI || code == ERR_SPECIAL) check_le_error(d, style);
   last_break = d.flags_h[FLAG_COUNT_A];
   int created = d.flags_h[FLAG_COUNT_B];
-  if (last_break != created) throw LammpsError("Numbers of created and broken bonds are not equal");
+  if (last_break != created) throw LammpsError(device_error_text(ERR_COUNT_MISMATCH, style));
+  check_le_error(d, style);
   if (last_break) eng->le_reneigh_step[fix_index(eng, this)] = eng->ntimestep;
 }
 
@@ -362,6 +358,7 @@ void FixExLoad::post_integrate() {
   int slot = le_slot(eng, this);
   if (slot >= LE_MAX_FIXES) throw LammpsError("MI355X engine supports at most " + std::to_string(LE_MAX_FIXES) + " extrusion/ex_load/ex_unload fixes");
   if (!rng_on_device) { le_rng_upload(d, slot, rng); rng_on_device = true; }
+  eng->le_style = style;
   // angles around new bonds only `if (atype && force->angle)` (fix_ex_load.cpp:236-240)
   const int angle_type_new = (atype > 0 && eng->angles_active()) ? atype : 0;
   if (angle_type_new > eng->nangletypes) throw LammpsError("Fix " + style + " angle type is invalid");
@@ -378,7 +375,7 @@ void FixExLoad::post_integrate() {
   }
   note_topology_changed(d);
   sync_flags(d);
-  check_le_error(d, style.c_str());
+  check_le_error(d, style);
   last_create = d.flags_h[FLAG_COUNT_A];
   total_create += last_create;
   eng->nbonds += last_create;
@@ -393,6 +390,7 @@ void FixExUnload::post_integrate() {
   int slot = le_slot(eng, this);
   if (slot >= LE_MAX_FIXES) throw LammpsError("MI355X engine supports at most " + std::to_string(LE_MAX_FIXES) + " extrusion/ex_load/ex_unload fixes");
   if (!rng_on_device) { le_rng_upload(d, slot, rng); rng_on_device = true; }
+  eng->le_style = style;
   if (eng->world > 1) {
     if (dd_le_fast(d)) dd_gather_needed(d, *eng->comm, btype, false); else dd_gather_positions(d, *eng->comm);
   }
@@ -400,7 +398,7 @@ void FixExUnload::post_integrate() {
   launch_ex_unload(d, p, slot);
   note_topology_changed(d);
   sync_flags(d);
-  check_le_error(d, style.c_str());
+  check_le_error(d, style);
   last_break = d.flags_h[FLAG_COUNT_A];
   total_break += last_break;
   eng->nbonds -= last_break;

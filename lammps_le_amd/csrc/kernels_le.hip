@@ -126,6 +126,36 @@ static void scan_local_order(DeviceState &d, const int *flag, int *out, int tota
 }
 
 // ------------------------------------------------------------------------------------------
+// Errors of a firing.  Several lanes can raise in one firing, and two of them different codes: the code that stays is the one
+// of the lowest rank below, whichever lane comes last - not the last store.  The ranks follow the order in which one firing
+// of the reference reaches its checks: the bondcount pass (fix_extrusion.cpp:292), then per new bond the full bond row and
+// the insert into the special row (fix_ex_load.cpp:558, :582; fix_extrusion.cpp:764), then update_topology's rebuilds (:818,
+// :837; :1081), and the angle overflow it only reports after its loop (:755).  ERR_ONE_SIDED, which the reference does not
+// have, sits where the counts are compared (:808), before the rebuilds.  Where the reference's serial loop would meet a full
+// bond row on one bead and a full special row on an EARLIER bead of the same firing it reports the special row; this engine
+// reports the bond row (fixed rank, no visit order).  A code that is no firing's (rank 0: Bad FENE bond, ...) is never replaced.
+__device__ __forceinline__ int le_error_rank(int code) {
+  switch (code) {
+    case ERR_NONE: return 99;
+    case ERR_EXT_MULTI: return 1;
+    case ERR_BPA: return 2;
+    case ERR_SPECIAL: return 3;
+    case ERR_ONE_SIDED: return 4;
+    case ERR_SPECIAL_SCRATCH: return 5;
+    case ERR_ANGLES: return 6;
+  }
+  return 0;
+}
+__device__ void dev_raise(int *__restrict__ flags, int code) {
+  int cur = atomicAdd(&flags[FLAG_ERROR], 0);
+  while (le_error_rank(code) < le_error_rank(cur)) {
+    const int seen = atomicCAS(&flags[FLAG_ERROR], cur, code);
+    if (seen == cur) break;
+    cur = seen;
+  }
+}
+
+// ------------------------------------------------------------------------------------------
 // special-list / bond-table edits on one bead (device versions of the reference's in-place code)
 __device__ __forceinline__ void dev_delete_bond(const Topo &tp, int i, int partner) {   // fix_extrusion.cpp:656-668
   int b = tp.bpa, nb = tp.num_bond[i];
@@ -191,7 +221,7 @@ __device__ void dev_rebuild_special_one(const Topo &tp, int m, int *__restrict__
     for (int j = 0; j < nn1; j++) if (sl[j] != m) copy[cn2++] = sl[j];
   }
   cn2 = dev_dedup(cn1, cn2, copy);
-  if (cn2 > ms) { flags[FLAG_ERROR] = ERR_SPECIAL_SCRATCH; return; }
+  if (cn2 > ms) { dev_raise(flags, ERR_SPECIAL_SCRATCH); return; }
   cn3 = cn2;
   for (int i = cn1; i < cn2; i++) {
     int n = copy[i];
@@ -200,7 +230,7 @@ __device__ void dev_rebuild_special_one(const Topo &tp, int m, int *__restrict__
     for (int j = 0; j < nn1; j++) if (sl[j] != m) copy[cn3++] = sl[j];
   }
   cn3 = dev_dedup(cn2, cn3, copy);
-  if (cn3 > ms) { flags[FLAG_ERROR] = ERR_SPECIAL_SCRATCH; return; }
+  if (cn3 > ms) { dev_raise(flags, ERR_SPECIAL_SCRATCH); return; }
   // the 1-2 block is unchanged: only the 1-3 / 1-4 blocks are rewritten, so concurrent rebuilds of
   // neighbours (which read only 1-2 blocks) see consistent data.  Its COUNT is stored as the reference stores it
   // (nspecial[m][0] = cn1, fix_extrusion.cpp:1104): a count that the unconditional decrements of a bond removal have
@@ -263,7 +293,7 @@ __device__ void dev_create_angles(const Topo &tp, int m, int atype, const int *_
   }
   tp.num_angle[m] = num;
   if (made) atomicAdd(&flags[FLAG_COUNT_B], made);
-  if (overflow) flags[FLAG_ERROR] = ERR_ANGLES;
+  if (overflow) dev_raise(flags, ERR_ANGLES);
 }
 // influence rules of update_topology: broken (fix_extrusion.cpp:940-969), created (:971-1001)
 // `angles`: fix ex_unload / bond/break with angles in the system (extrusion leaves angles alone, fix_extrusion.cpp:924-1002)
@@ -312,7 +342,7 @@ __global__ __launch_bounds__(BLOCK) void k_le_gather(Topo tp, const double4 *__r
   int bc = 0, nb = tp.num_bond[t];
   for (int m = 0; m < nb; m++) if (tp.bond_type[(size_t)t * tp.bpa + m] == btype) bc++;
   bondcount[t] = bc;
-  if (check_multi && bc > 1) flags[FLAG_ERROR] = ERR_EXT_MULTI;
+  if (check_multi && bc > 1) dev_raise(flags, ERR_EXT_MULTI);
 }
 __device__ __forceinline__ double d2(const double4 &a, const double4 &b) {
   double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
@@ -603,12 +633,12 @@ __global__ __launch_bounds__(BLOCK) void k_exload_create(Topo tp, ExLoadParams P
       }
       if (ok) {
         int nb = tp.num_bond[t];
-        if (nb == tp.bpa) { flags[FLAG_ERROR] = ERR_BPA; }
+        if (nb == tp.bpa) { dev_raise(flags, ERR_BPA); }
         else {
           tp.bond_type[(size_t)t * tp.bpa + nb] = P.btype;
           tp.bond_atom[(size_t)t * tp.bpa + nb] = j;
           tp.num_bond[t] = nb + 1;
-          if (!dev_special_insert12(tp, t, j)) flags[FLAG_ERROR] = ERR_SPECIAL;
+          if (!dev_special_insert12(tp, t, j)) dev_raise(flags, ERR_SPECIAL);
           int c = bc[t] + 1;
           bc[t] = c;
           int ty = tp.type_t[t], nty = ty;
@@ -1076,14 +1106,23 @@ __global__ __launch_bounds__(BLOCK) void k_ext_create(Topo tp, int btype, const 
   int j = to_add[i];
   if (j == 0 || to_add[j] != i) return;
   int nb = tp.num_bond[i];
-  if (nb == tp.bpa) return;
   int lb = i < j ? i : j, rb = i < j ? j : i;
-  if ((tr[lb + 1] == rb && tr[rb] == lb + 1) || (tr[lb + 1] == rb - 1 && tr[rb - 1] == lb + 1) ||
-      (tr[lb] == rb - 1 && tr[rb - 1] == lb)) {
+  const bool moves = (tr[lb + 1] == rb && tr[rb] == lb + 1) || (tr[lb + 1] == rb - 1 && tr[rb - 1] == lb + 1) ||
+                     (tr[lb] == rb - 1 && tr[rb - 1] == lb);
+  if (nb == tp.bpa) {
+    // a full end is skipped without a word (fix_extrusion.cpp:707-708).  The lower end counts the bond: skipped, the
+    // created count falls short and the run ends at :808, here as there.  The higher end does not count it: the counts
+    // agree and the reference runs on with the bond stored by the lower end alone - which this engine cannot hold (a bond
+    // acts on each end from that end's own table), so the firing ends in ERR_ONE_SIDED instead.  (Both ends full: the lower
+    // one's missing count decides, FixExtrusion::post_integrate compares the counts first.)
+    if (moves && i > j) dev_raise(flags, ERR_ONE_SIDED);
+    return;
+  }
+  if (moves) {
     tp.bond_type[(size_t)i * tp.bpa + nb] = btype;
     tp.bond_atom[(size_t)i * tp.bpa + nb] = j;
     tp.num_bond[i] = nb + 1;
-    if (!dev_special_insert12(tp, i, j)) flags[FLAG_ERROR] = ERR_SPECIAL;
+    if (!dev_special_insert12(tp, i, j)) dev_raise(flags, ERR_SPECIAL);
     bc[i]++;
     fin_add[i] = j;
     if (i < j) atomicAdd(&flags[FLAG_COUNT_B], 1);

@@ -111,6 +111,10 @@ static int seterr(leo_t *s, const char *m) {
   if (!s->errflag) { snprintf(s->err, sizeof s->err, "%s", m); s->errflag = 1; }
   return 1;
 }
+static int seterr2(leo_t *s, const char *m, const char *tail) {
+  if (!s->errflag) { snprintf(s->err, sizeof s->err, "%s%s", m, tail); s->errflag = 1; }
+  return 1;
+}
 
 /* ===================== RanMars: src/random_mars.cpp:29-95 ===================== */
 void leo_ranmars_init(leo_ranmars *r, int seed) {
@@ -1119,8 +1123,12 @@ static int le_dedup(int nstart, int nstop, int *copy) {
   }
   return nstop;
 }
-/* rebuild_special_one: src/USER-LE/fix_extrusion.cpp:1045-1108 */
-static int rebuild_special_one(leo_t *s, int m) {
+/* rebuild_special_one: src/USER-LE/fix_extrusion.cpp:1045-1108.  Every fix has its own copy, and the copies differ in the text
+   of the overflow error: fix extrusion's says `bond/create` (:1081, :1101), fix ex_load's says `ex_load` (fix_ex_load.cpp:818,
+   :837), stock bond/create's its own name (MC/fix_bond_create.cpp:784, :803); the copies of ex_unload and bond/break do not
+   check at all (a row rebuilt after a break that outgrows the table overruns it in the reference: no recorded run gets
+   there, and this oracle stops with fix extrusion's text).  `style`: the name the text ends in. */
+static int rebuild_special_one(leo_t *s, int m, const char *style) {
   int ms = s->maxspecial; int *copy = s->copy;
   int *slist = s->special + (size_t)m * ms;
   int n1 = s->nspecial[3 * m], cn1 = 0, cn2, cn3;
@@ -1133,7 +1141,7 @@ static int rebuild_special_one(leo_t *s, int m) {
     for (int j = 0; j < nn1; j++) if (sl[j] != s->tag[m]) copy[cn2++] = sl[j];
   }
   cn2 = le_dedup(cn1, cn2, copy);
-  if (cn2 > ms) return seterr(s, "Special list size exceeded in fix bond/create");
+  if (cn2 > ms) return seterr2(s, "Special list size exceeded in fix ", style);
   cn3 = cn2;
   for (int i = cn1; i < cn2; i++) {
     int n = map_(s, copy[i]);
@@ -1142,7 +1150,7 @@ static int rebuild_special_one(leo_t *s, int m) {
     for (int j = 0; j < nn1; j++) if (sl[j] != s->tag[m]) copy[cn3++] = sl[j];
   }
   cn3 = le_dedup(cn2, cn3, copy);
-  if (cn3 > ms) return seterr(s, "Special list size exceeded in fix bond/create");
+  if (cn3 > ms) return seterr2(s, "Special list size exceeded in fix ", style);
   s->nspecial[3 * m] = cn1; s->nspecial[3 * m + 1] = cn2; s->nspecial[3 * m + 2] = cn3;
   memcpy(slist, copy, cn3 * sizeof(int));
   return 0;
@@ -1166,7 +1174,7 @@ static int topo_broken(leo_t *s, int nbreak, const int *broken, int angles) {
       influenced = 1;
       if (angles) break_angles(s, i, id1, id2, &nang);
     }
-    if (influenced && rebuild_special_one(s, i)) return 1;
+    if (influenced && rebuild_special_one(s, i, "bond/create")) return 1;
   }
   s->nangles -= nang / 3;
   return 0;
@@ -1187,7 +1195,7 @@ static int topo_created(leo_t *s, int ncreate, const int *created, leo_fix *fx) 
         for (int k = 0; k < n; k++) if (slist[k] == id1 || slist[k] == id2) { influenced = 1; break; }
       }
     }
-    if (influenced && rebuild_special_one(s, i)) return 1;
+    if (influenced && rebuild_special_one(s, i, fx && fx->kind == FIX_EX_LOAD ? "ex_load" : "bond/create")) return 1;
     if (influenced && angleflag && create_angles(s, fx, i, ncreate, created, &nang)) return 1;
   }
   s->nangles += nang / 3;

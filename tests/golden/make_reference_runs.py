@@ -11,6 +11,12 @@ A scenario is written only if (a) the reference exits 0 without ERROR (FENE warn
 of three reruns from starts moved by one ulp per coordinate are the recorded ones at every step, (c) every LE fix fired and
 at least min_ext type-2 bonds exist at the end, (d) the scenario's own point is reached (reference_runs.reached, and the
 contrast run ends elsewhere).  The spread of those three reruns is what the tests take their bounds from.
+
+A limit scenario (reference_runs.LIMITS -> ref_limit_*.npz, the `limits` entry of ref_runs.json) is a run that is MEANT to end
+in an ERROR: it is recorded with dumps after every step, flushed, and written only if the base run and the three perturbed
+reruns end with the same text at the same step after the same integer rows, one kind of ERROR line appears, and the bead the
+error is about sits at its limit after the last complete step (make_limit, reference_runs.limit_conditions).  Stored: the
+text without its `ERROR on proc N:` prefix and `(file:line)` suffix, the step, and the state after the last complete step.
 """
 import hashlib
 import json
@@ -52,8 +58,9 @@ def savez_lzma(path, **arrays):
                 np.lib.format.write_array(fh, np.asanyarray(arr), allow_pickle=False)
 
 
-def run_lmp(script, system, work, data_name):
-    """Write the data file, run the reference on the script; -> (log text, sha256 of the data file)."""
+def run_lmp(script, system, work, data_name, may_abort=False):
+    """Write the data file, run the reference on the script; -> (log text, sha256 of the data file).  may_abort: a limit
+    scenario, whose ERROR is the point (the caller reads it from the log)."""
     data = os.path.join(work, data_name)
     write_data(data, system)
     script = re.sub(r"^read_data \S+", "read_data " + data, script, flags=re.M)
@@ -63,7 +70,7 @@ def run_lmp(script, system, work, data_name):
     log = os.path.join(work, "log.out")
     rc = subprocess.call([LMP, "-in", inp, "-log", log, "-screen", "none", "-echo", "none"], cwd=work)
     text = open(log).read() if os.path.exists(log) else ""
-    if rc != 0 or "ERROR" in text:
+    if (rc != 0 or "ERROR" in text) and not may_abort:
         raise Refused("(a) the reference exited %d: %s" % (rc, "; ".join(ln for ln in text.split("\n") if "ERROR" in ln)[:300]))
     return text, hashlib.sha256(open(data, "rb").read()).hexdigest()
 
@@ -78,6 +85,8 @@ def read_dump(path):
             while not (lines[i].startswith("ITEM: ATOMS") or lines[i].startswith("ITEM: ENTRIES")):
                 i += 1
             rows = [ln.split() for ln in lines[i + 1:i + 1 + n]]
+            if len(rows) < n or (n and len(rows[-1]) != len(rows[0])):          # (a frame the abort of a limit run cut short)
+                break
             out[step] = np.array(rows, dtype=np.float64).reshape(n, -1)
             i += 1 + n
         else:
@@ -164,7 +173,10 @@ def record(scn, system, work, tag):
     out["bond"] = delta_rows({s: a[:, :4] for s, a in bonds.items()}, cps[-1])
     if rr.has_angles(scn):
         out["angle"] = delta_rows(read_dump(prefix + ".angles"), cps[-1])
-    for name in (".state", ".bonds", ".angles"):
+    if scn.get("limit"):
+        a = read_dump(prefix + ".nbonds")[cps[-1]]
+        out["num_bond"] = a[np.argsort(a[:, 0], kind="stable"), 1].astype(np.int32)
+    for name in (".state", ".bonds", ".angles", ".nbonds"):
         if os.path.exists(prefix + name):
             os.remove(prefix + name)
     return out
@@ -219,6 +231,8 @@ def make_scenario(scn, work, melts, out=HERE):
         arrays["start_file_order"] = np.asarray(system["file_order"], dtype=np.int32)
     if "angle" in base:
         arrays.update(angle_steps=base["angle"][0], angle_offsets=base["angle"][1], angle_rows=base["angle"][2])
+    if "num_bond" in base:
+        arrays["num_bond"] = base["num_bond"]
     meta = dict(data_sha256=base["sha"], fene_warnings=base["fene"], spread=spread, contrast_differs=contrast_differs,
                 steps=cps[-1], perturbed_reruns=NPERTURB, perturbed_rows_identical=True, longest_extruder_bond=base["longest"])
     # (c), (d) on what would be written
@@ -230,7 +244,98 @@ def make_scenario(scn, work, melts, out=HERE):
     with np.load(tmp) as z:
         fx.z = {k: z[k] for k in z.files}
     fx.system = lambda: system
-    why = rr.fixture_conditions(fx)
+    fx.error = fx.error_step = None
+    why = rr.limit_conditions(fx) if scn.get("limit") else rr.fixture_conditions(fx)
+    if why:
+        os.remove(tmp)
+        raise Refused(why)
+    os.replace(tmp, path)
+    return meta
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# limit scenarios: the reference is meant to abort
+# ------------------------------------------------------------------------------------------------------------------
+ERROR_LINE = re.compile(r"^ERROR(?: on proc \d+)?: (.*?)(?: \(\S+:\d+\))?\s*$", re.M)
+
+
+def record_limit(scn, system, work, tag):
+    """One reference run of a limit scenario (dumps after every step, flushed) -> what survived the abort: the error text
+    without its `ERROR on proc N:` prefix and `(file:line)` suffix, the last complete step S, the state and rows up to S."""
+    os.makedirs(work, exist_ok=True)
+    prefix = os.path.join(work, tag)
+    text, sha = run_lmp(rr.reference_script(scn, prefix, 1), system, work, "data.chain", may_abort=True)
+    errors = ERROR_LINE.findall(text)
+    if not errors:
+        raise Refused("the reference ran to the end: no ERROR")
+    states, bonds, counts = read_dump(prefix + ".state"), read_dump(prefix + ".bonds"), read_dump(prefix + ".nbonds")
+    angles = read_dump(prefix + ".angles") if rr.has_angles(scn) else None
+    thermo = read_thermo(text, len(rr.thermo_columns(scn)))
+    last = min(max(states), max(bonds), max(counts), int(thermo[-1, 0]), *([max(angles)] if angles else []))
+    a = states[last]
+    local_order = a[:, 0].astype(np.int32)
+    a = a[np.argsort(a[:, 0], kind="stable")]
+    assert np.array_equal(a[:, 0], np.arange(1, len(a) + 1))
+    c = counts[last]
+    start = states[0][np.argsort(states[0][:, 0], kind="stable")]
+    out = dict(errors=errors, last=last, sha=sha, fene=len(re.findall("FENE bond too long", text)), thermo=thermo[thermo[:, 0] == last][-1:],
+               type=a[:, 1].astype(np.int32), x=a[:, 2:5], image=a[:, 5:8].astype(np.int32), v=a[:, 8:11], local_order=local_order,
+               num_bond=c[np.argsort(c[:, 0], kind="stable"), 1].astype(np.int32), start_x=start[:, 2:5],
+               start_image=start[:, 5:8].astype(np.int32), bond=delta_rows({s: b[:, :4] for s, b in bonds.items()}, last))
+    if angles:
+        out["angle"] = delta_rows(angles, last)
+    for name in (".state", ".bonds", ".angles", ".nbonds"):
+        if os.path.exists(prefix + name):
+            os.remove(prefix + name)
+    return out
+
+
+def make_limit(scn, work, melts, out=HERE):
+    """A limit scenario is written only if the base run and the three perturbed reruns end with the same text at the same
+    step and with the same integer rows before it, exactly one kind of ERROR line appears, and the bead the error is about
+    sits at its limit after the last complete step (reference_runs.limit_conditions)."""
+    if scn["runs_on"]:
+        return make_scenario(scn, work, melts, out)
+    name, p = scn["name"], scn["system"]
+    system = rr.build_system(scn, melt=melts(p["n"], p.get("nchains", 1), p.get("seed", 1)))
+    base = record_limit(scn, system, os.path.join(work, name), "base")
+    if not (np.array_equal(base["start_x"], system["x"]) and np.array_equal(base["start_image"], system["image"])):
+        raise Refused("the reference's step-0 state is not the written start")
+    last, L = base["last"], box_lengths(system)
+    spread = dict(x={str(last): 0.0}, v={str(last): 0.0}, thermo=np.zeros_like(base["thermo"][:, 1:]))
+    for d in range(NPERTURB):
+        run = record_limit(scn, perturbed(system, d), os.path.join(work, name), "p%d" % d)
+        if run["errors"] != base["errors"] or run["last"] != last:
+            raise Refused("(b) perturbed rerun %d ends with %r after step %d, not %r after step %d" % (d, run["errors"], run["last"], base["errors"], last))
+        if not same_rows(run["bond"], base["bond"]) or ("angle" in base and not same_rows(run["angle"], base["angle"])):
+            raise Refused("(b) bond or angle rows changed in perturbed rerun %d" % d)
+        if not all(np.array_equal(run[k], base[k]) for k in ("type", "image", "local_order", "num_bond")):
+            raise Refused("(b) types, image flags, bond counts or local order changed in perturbed rerun %d" % d)
+        ux = (run["x"] + run["image"] * L) - (base["x"] + base["image"] * L)
+        spread["x"][str(last)] = max(spread["x"][str(last)], float(np.abs(ux).max()))
+        spread["v"][str(last)] = max(spread["v"][str(last)], float(np.abs(run["v"] - base["v"]).max()))
+        spread["thermo"] = np.maximum(spread["thermo"], np.abs(run["thermo"][:, 1:] - base["thermo"][:, 1:]))
+    spread["thermo"] = spread["thermo"].tolist()
+    arrays = dict(checkpoints=np.array([last], dtype=np.int32), thermo=base["thermo"], local_order=base["local_order"],
+                  num_bond=base["num_bond"], bond_steps=base["bond"][0], bond_offsets=base["bond"][1], bond_rows=base["bond"][2],
+                  start_type=np.asarray(system["type"], dtype=np.int32))
+    if last > 0:          # (after step 0 the state is the start itself, compared above)
+        arrays.update(x=base["x"][None], v=base["v"][None], type=base["type"][None], image=base["image"][None])
+    if "angle" in base:
+        arrays.update(angle_steps=base["angle"][0], angle_offsets=base["angle"][1], angle_rows=base["angle"][2])
+    meta = dict(error=base["errors"][0], error_step=last + 1, error_kinds=len(set(base["errors"])), data_sha256=base["sha"],
+                fene_warnings=base["fene"], spread=spread, steps=last, perturbed_reruns=NPERTURB, perturbed_same_error=True,
+                perturbed_rows_identical=True)
+    path = os.path.join(out, "ref_%s.npz" % name)
+    tmp = path + ".tmp"
+    savez_lzma(tmp, **arrays)
+    fx = rr.Fixture.__new__(rr.Fixture)
+    fx.name, fx.scn, fx.meta, fx.checkpoints, fx.last, fx.columns = name, scn, meta, [last], last, rr.thermo_columns(scn)
+    fx.error, fx.error_step = meta["error"], meta["error_step"]
+    with np.load(tmp) as z:
+        fx.z = {k: z[k] for k in z.files}
+    fx.system = lambda: system
+    why = rr.limit_conditions(fx)
     if why:
         os.remove(tmp)
         raise Refused(why)
@@ -259,9 +364,10 @@ def make_ranmars(work):
 def main(argv):
     if not os.path.isfile(LMP):
         sys.exit("make_reference_runs: build oracle/_ref/lmp first (python oracle/build_ref.py)")
-    want = argv or rr.NAMES + ["ranmars"]
+    want = argv or rr.NAMES + rr.LIMIT_NAMES + ["ranmars"]          # (twins before the limit scenarios that name them)
     meta_path = os.path.join(HERE, "ref_runs.json")
     meta = json.load(open(meta_path)) if (argv and os.path.exists(meta_path)) else dict(scenarios={})
+    meta.setdefault("limits", {})
     meta["build"] = json.load(open(INFO))
     meta["factor"] = rr.FACTOR
     work = tempfile.mkdtemp(prefix="refruns_")
@@ -280,6 +386,8 @@ def main(argv):
             try:
                 if name == "ranmars":
                     meta["ranmars"] = make_ranmars(os.path.join(work, "ranmars"))
+                elif name in rr.LIMIT_BY_NAME:
+                    meta["limits"][name] = make_limit(rr.LIMIT_BY_NAME[name], work, melts)
                 else:
                     meta["scenarios"][name] = make_scenario(rr.BY_NAME[name], work, melts)
                 print("recorded", name)

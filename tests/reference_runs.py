@@ -83,6 +83,17 @@ def build_system(scn, melt=None, recorded=None):
         ang = [(1, i, i + 1, i + 2) for i in range(1, n - 1) if (i - 1) // per == (i + 1) // per]
         s["nangletypes"], s["angles"], s["extra_angle"] = 2, np.array(ang, dtype=np.int32), 24
         s["atom_style"] = "molecular"
+    # the capacities of the limit scenarios and their twins (the `extra ... per atom` lines of the data file), extruder bonds
+    # the data file already holds (rows (a, b) of type 2), and single beads given another type
+    for k in ("extra_bond", "extra_special", "extra_angle"):
+        if k in p:
+            s[k] = p[k]
+    if p.get("ext_bonds"):
+        s["bonds"] = np.concatenate([s["bonds"], np.array([(2, a, b) for a, b in p["ext_bonds"]], dtype=np.int32)])
+    if p.get("type_at") and recorded is None:
+        s["type"] = np.array(s["type"], dtype=np.int32)
+        for tag, t in p["type_at"]:
+            s["type"][tag - 1] = t
     return s
 
 
@@ -215,12 +226,84 @@ SCENARIOS = [
     _scn("velocity_loop_local", BAR, le_script(tp=0.5, **_CYCLE) + "velocity all create 1.0 4928 loop local\nrun 32\n"
          "velocity all create 1.2 777 loop local\nrun 32\n", contrast=("create 1.2 777 loop local", "create 1.2 777 loop all")),
     # the barrier cycle and the sorted one for 2 and 3 z slabs
-    _scn("slabs_cycle", _SLABS, _DD + "run 60\n", steps=60, contrast=("1 2 3 0.5 2 4", "1 2 3 1.0 2 4"), point="along_z"),
+    _scn("slabs_cycle", _SLABS, _DD + "run 60\n", steps=60, contrast=("1 2 3 0.5 2 4", "1 2 3 1.0 2 4"), point="along_z+full_bond"),
     _scn("slabs_sort", _SLABS, _sorted(_DD, 3) + "run 60\n", steps=60, contrast=("atom_modify sort 3 0", "atom_modify sort 0 0"),
          point="along_z+sorted"),
+    # fix langevin with a temperature ramp (Tstart 1.0, Tstop 2.0 over the run)
+    _scn("langevin_ramp", BAR, le_script(tp=0.5, **_CYCLE).replace("1.0 1.0 1.0 904297", "1.0 2.0 1.0 904297") + "run 64\n",
+         contrast=("1.0 2.0 1.0 904297", "1.0 1.0 1.0 904297"), family="langevin"),
+]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# limit scenarios: runs of the reference that END IN AN ERROR because one per-atom row is one slot short, and their twins
+# ------------------------------------------------------------------------------------------------------------------
+# A limit scenario is a script the reference aborts; its fixture (ref_limit_*.npz) holds the error text, the step, and the
+# state after the last complete step.  Its twin is the same script with that one capacity (`extra bond / special / angle per
+# atom`) one larger and nothing else changed: an ordinary scenario that runs to the end, whose point is that some bead ends
+# with that row exactly full (full_bond, full_special, full_angle) - with every row of every tag compared exactly, a store
+# one slot too far shows.  Two twins are scenarios that existed before (slabs_cycle, stock_create).  limit_load_bpa runs the
+# slab scenario's script (iparam 1 1): ex_load bonds only beads that hold exactly two bonds, so its maxbond never decides.
+def _without(script, *ids):
+    return "\n".join(ln for ln in script.split("\n") if not any(ln.startswith("fix %s " % i) for i in ids))
+
+
+_CYC = le_script(tp=0.5, **_CYCLE)
+_LOAD_ONLY = _without(le_script(nl=5, lprob="prob 0.8 684474"), "loop", "unloading")
+# one extruder bond across the junction of two chains (beads 250 | 251 of four chains of 250): both of its ends hold two
+# bonds, every bead it can step to holds two, and with `extra bond per atom` 0 two is all a row has.  tp = 0: a barrier bead
+# of the blocking side never lets the extruder through, so exactly one end tries to step (thermo 1: the one move is printed)
+_EXT_ONLY = _without(le_script(n1=4, tp=0.0, lr=""), "loading", "unloading").replace("thermo 10", "thermo 1")
+_JUNCTION = dict(n=N, nchains=4, seed=2, ext_bonds=[(250, 251)])
+_ANG = dict(n=N, nchains=2, seed=6, angles=True)
+_ANG_SCRIPT = ANGLES % ("harmonic", "3.0 170.0", "1.0 100.0")
+
+SCENARIOS += [
+    _scn("twin_load_rebuild_special", dict(BAR, extra_special=5), _LOAD_ONLY + "run 48\n", steps=48, fixes=("loading",),
+         point="full_special"),
+    _scn("twin_load_angles", dict(_ANG, extra_angle=12), _ANG_SCRIPT + "run 28\n", steps=28, point="full_angle"),
+    _scn("twin_ext_bpa_low", dict(_JUNCTION, type_at=[(252, 3)], extra_bond=1), _EXT_ONLY + "run 48\n", steps=48, fixes=("loop",),
+         point="full_bond", min_ext=1),
+    _scn("twin_ext_rebuild_special", dict(BAR, extra_special=12), _CYC + "run 48\n", steps=48, point="full_special"),
 ]
 BY_NAME = {s["name"]: s for s in SCENARIOS}
 NAMES = [s["name"] for s in SCENARIOS]
+BY_NAME["stock_create"]["point"] += "+full_bond"
+
+
+def _limit(name, system, script, steps, at_limit, twin=None, fixes=LE3, runs_on=False, **kw):
+    """at_limit: what reached() asks of the last complete step (bond: a bead with num_bond == bond_per_atom; special12: the 1-2
+    block alone fills the special row; multi: a bead with two extruder bonds; twin: the row that overflows is rebuilt whole, no
+    bead need be full before - the twin, one slot larger, ends full instead).  runs_on: the reference does NOT stop."""
+    s = _scn(name, system, script + "run %d\n" % steps, steps=steps, fixes=fixes, **kw)
+    s.update(at_limit=at_limit, twin=twin, runs_on=runs_on, limit=True)
+    return s
+
+
+LIMITS = [
+    # (the slab system and script of slabs_cycle: the GPU suite also runs this one on two ranks)
+    _limit("limit_load_bpa", dict(_SLABS, extra_bond=0), _DD, 48, "bond", twin="slabs_cycle"),
+    # special_bonds fene trims the 1-3 and 1-4 blocks (weights 1.0): a bead no fix has touched lists its two 1-2 partners, and
+    # with `extra special per atom` 0 that is the whole row.  No twin: with one slot more the insert passes and the rebuild
+    # that follows (7 entries) overflows - that run is limit_load_rebuild_special's kind
+    _limit("limit_load_special", dict(BAR, extra_special=0), _CYC, 48, "special12"),
+    _limit("limit_load_rebuild_special", dict(BAR, extra_special=4), _LOAD_ONLY, 48, "twin", twin="twin_load_rebuild_special",
+           fixes=("loading",)),
+    _limit("limit_load_angles", dict(_ANG, extra_angle=11), _ANG_SCRIPT, 28, "twin", twin="twin_load_angles"),
+    _limit("limit_ext_multi", dict(BAR, ext_bonds=[(10, 12), (10, 14)], extra_bond=0), _CYC, 48, "multi"),
+    _limit("limit_ext_bpa_low", dict(_JUNCTION, type_at=[(252, 3)], extra_bond=0), _EXT_ONLY, 48, "bond", twin="twin_ext_bpa_low",
+           fixes=("loop",)),
+    _limit("limit_ext_bpa_high", dict(_JUNCTION, type_at=[(249, 2)], extra_bond=0), _EXT_ONLY, 48, "bond", fixes=("loop",),
+           runs_on=True, point="one_sided", min_ext=1),
+    _limit("limit_ext_rebuild_special", dict(BAR, extra_special=11), _CYC, 48, "twin", twin="twin_ext_rebuild_special"),
+    _limit("limit_create_bpa", dict(n=N, types=("sticky",), extra_bond=0), STOCK % "", 60, "bond", twin="stock_create",
+           fixes=("creating", "breaking")),
+    _limit("limit_create_special", dict(n=N, types=("sticky",), extra_special=0), STOCK % "", 60, "special12",
+           fixes=("creating", "breaking")),
+]
+LIMIT_BY_NAME = {s["name"]: s for s in LIMITS}
+LIMIT_NAMES = [s["name"] for s in LIMITS]
+ERROR_LIMITS = [s["name"] for s in LIMITS if not s["runs_on"]]
 
 
 def has_angles(scn):
@@ -244,6 +327,13 @@ def record_lines(scn, prefix, every):
     if has_angles(scn):
         out += ["compute rra all property/local atype aatom1 aatom2 aatom3",
                 "dump rra all local 1 %s.angles index c_rra[1] c_rra[2] c_rra[3] c_rra[4]" % prefix]
+    if scn.get("limit"):
+        # a run that is meant to abort: every dump and the thermo output flushed after every step, so that the last complete
+        # step survives; thermo after every step (the row of the last complete step is the one kept); and the per-atom bond
+        # count, which the bond rows cannot give once a bond is stored by one end only
+        out += ["compute rrn all property/atom nbonds", "dump rrn all custom %d %s.nbonds id c_rrn" % (every, prefix),
+                "thermo 1", "thermo_modify flush yes"]
+        out += ["dump_modify %s flush yes" % d for d in ["rrb", "rrs", "rrn"] + (["rra"] if has_angles(scn) else [])]
     return "\n".join(out) + "\n"
 
 
@@ -253,6 +343,38 @@ def reference_script(scn, prefix, every):
     first_run = next(i for i, ln in enumerate(lines) if ln.startswith("run "))
     assert all(ln.startswith(("run ", "velocity ", "run_style")) or not ln for ln in lines[k:]) and first_run >= k
     return "\n".join(lines[:k]) + "\n" + record_lines(scn, prefix, every) + "\n".join(lines[k:])
+
+
+def capacities(system):
+    """bond_per_atom, maxspecial and angle_per_atom as read_data sets them for a start system: the largest count in the file
+    plus the `extra ... per atom` line.  Every script here says `special_bonds fene`, whose 1-3 and 1-4 weights of 1.0 make
+    the special build keep the 1-2 block only (Special::trim): the longest row of the file is the largest bond count."""
+    n = len(system["x"])
+    nb = np.bincount(np.asarray(system["bonds"])[:, 1:].reshape(-1) - 1, minlength=n).max()
+    out = dict(bond=int(nb + system.get("extra_bond", 0)), special=int(nb + system.get("extra_special", 0)), angle=0)
+    if system.get("nangletypes"):          # (newton_bond off: an angle of the file is stored at its three atoms)
+        out["angle"] = int(np.bincount(np.asarray(system["angles"])[:, 1:].reshape(-1) - 1, minlength=n).max() + system.get("extra_angle", 0))
+    return out
+
+
+def bonds_per_bead(rows, n):
+    return np.bincount(np.asarray(rows)[:, 1:].reshape(-1) - 1, minlength=n)
+
+
+def within_three_bonds(rows, n):
+    """Per bead the number of other beads at most three bonds away: the length of a special row that has been rebuilt whole
+    (1-2, 1-3 and 1-4 partners, each once)."""
+    nbr = [set() for _ in range(n)]
+    for _, a, b in np.asarray(rows):
+        nbr[a - 1].add(b - 1), nbr[b - 1].add(a - 1)
+    out = np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        seen, edge = {i}, {i}
+        for _ in range(3):
+            edge = set().union(*[nbr[j] for j in edge]) - seen if edge else set()
+            seen |= edge
+        out[i] = len(seen) - 1
+    return out
 
 
 def script_for_steps(scn, steps):
@@ -269,6 +391,16 @@ def script_for_steps(scn, steps):
             break
         out.append(ln)
     assert left == 0, (scn["name"], steps)
+    # a temperature ramp runs from Tstart to Tstop over the steps of the run command: the cut run ramps to the temperature the
+    # full run has reached at the cut (1.0 -> 2.0 over 64 steps: a multiple of 1/64, exact in binary; the target of a step
+    # then differs from the full run's by the rounding of step / steps * (steps / 64) alone)
+    total = sum(int(ln.split()[1]) for ln in scn["script"].split("\n") if ln.startswith("run "))
+    for k, ln in enumerate(out):
+        w = ln.split()
+        if w[:1] == ["fix"] and w[3] == "langevin" and w[4] != w[5] and steps != total:
+            assert scn["script"].count("\nrun ") == 1 and steps > 0
+            w[5] = repr(float(w[4]) + (float(w[5]) - float(w[4])) * steps / total)
+            out[k] = " ".join(w)
     return "\n".join(out) + "\n"
 
 
@@ -280,11 +412,14 @@ class Fixture:
 
     def __init__(self, name):
         import json
-        self.name, self.scn = name, BY_NAME[name]
+        limit = name in LIMIT_BY_NAME
+        self.name, self.scn = name, (LIMIT_BY_NAME if limit else BY_NAME)[name]
         with np.load(os.path.join(GOLDEN, "ref_%s.npz" % name)) as z:
             self.z = {k: z[k] for k in z.files}
         with open(os.path.join(GOLDEN, "ref_runs.json")) as fh:
-            self.meta = json.load(fh)["scenarios"][name]
+            self.meta = json.load(fh)["limits" if limit else "scenarios"][name]
+        # (a limit fixture: one checkpoint, the last complete step; the error came in the step after it)
+        self.error, self.error_step = self.meta.get("error"), self.meta.get("error_step")
         self.checkpoints = [int(c) for c in self.z["checkpoints"]]
         self.last = self.checkpoints[-1]
         self.columns = thermo_columns(self.scn)
@@ -309,6 +444,9 @@ class Fixture:
 
     def state(self, step):
         k = self.checkpoints.index(step)
+        if "x" not in self.z:          # a run that ended in its first step: its last complete state is the start it read, which
+            s = self.system()          # the generator has compared with the reference's own step-0 dump bit for bit
+            return dict(x=np.asarray(s["x"]), v=np.asarray(s["v"]), type=np.asarray(s["type"]), image=np.asarray(s["image"]))
         return {q: self.z[q][k] for q in ("x", "v", "type", "image")}
 
     def unwrapped(self, x, image):
@@ -555,7 +693,73 @@ def _reached(fx, point):
         steps = fx.change_steps("angle")
         shrank = any(len(fx.angles_at(steps[k + 1])) < len(fx.angles_at(steps[k])) for k in range(len(steps) - 1))
         return bool((a[:, 0] == 2).any() and shrank and counts.max() > counts[0])
+    n, cap = scn["system"]["n"], capacities(fx.system())
+    if point == "full_bond":      # a twin: some bead ends with its bond row exactly full
+        return bool(bonds_per_bead(rows, n).max() == cap["bond"])
+    if point == "full_special":   # some bead ends with a rebuilt special row exactly as long as the row is
+        return bool(within_three_bonds(rows, n).max() == cap["special"])
+    if point == "full_angle":     # the reference writes no per-atom angle count (and ex_load does not store a new angle at all
+        return full_angle(fx)     # three atoms, so the rows do not give it): see full_angle
+    if point == "one_sided":      # a bond that one end alone stores: the rows count more bonds on a bead than it holds
+        return bool((bonds_per_bead(rows, n) != fx.z["num_bond"]).sum() == 1)
     return True
+
+
+def full_angle(fx):
+    """The twin of the angle limit ends with an angle row exactly full.  The count comes from the oracle at the end of the
+    recorded run (its angle rows, the centre copies, are the recorded ones there: check_discrete), bounded from below by the
+    recorded rows: centre copies + the end copies ex_load makes."""
+    from systems import run_oracle
+    o = run_oracle(fx.scn["script"], fx.system())
+    table = o.angle_table()
+    return bool(np.array_equal(angle_rows(*table), fx.angles_at(fx.last)) and table[0].max() == capacities(fx.system())["angle"])
+
+
+def at_limit(fx):
+    """A limit fixture: the bead the error names sits at its limit after the last complete step (LIMITS: at_limit)."""
+    kind, n, cap = fx.scn["at_limit"], fx.scn["system"]["n"], capacities(fx.system())
+    rows = fx.rows_at(fx.last)
+    if kind == "bond" and fx.scn["runs_on"]:          # (the bead that could not store its end of the new bond is still full)
+        short = np.nonzero(bonds_per_bead(rows, n) != fx.z["num_bond"])[0]
+        return bool(len(short) == 1 and fx.z["num_bond"][short[0]] == cap["bond"])
+    if kind == "bond":
+        return bool(bonds_per_bead(rows, n).max() == cap["bond"] and np.array_equal(bonds_per_bead(rows, n), fx.z["num_bond"]))
+    if kind == "special12":       # no fix has acted yet (the rows are the file's), so every row is its 1-2 block alone
+        return bool(np.array_equal(rows, sort_rows(np.asarray(fx.system()["bonds"]))) and bonds_per_bead(rows, n).max() == cap["special"])
+    if kind == "multi":
+        ext = rows[rows[:, 0] == 2]
+        return bool(np.bincount(ext[:, 1:].reshape(-1)).max() == 2)
+    if kind == "twin":            # a row rebuilt whole overflows from any length below: the twin, one slot longer, ends full
+        return bool(reached(fixture(fx.scn["twin"])))
+    return False
+
+
+def limit_conditions(fx):
+    """What the generator asks of a limit scenario before it writes it, and the tests of the committed file: one kind of
+    ERROR, at one step, in all four runs; the bead at its limit; the twin there, the same script with one slot more."""
+    scn = fx.scn
+    if scn["runs_on"]:
+        return fixture_conditions(fx) or ("" if at_limit(fx) else "the full bead is not full")
+    m = fx.meta
+    if not (m["error_kinds"] == 1 and m["perturbed_reruns"] == 3 and m["perturbed_same_error"] is True and m["perturbed_rows_identical"] is True):
+        return "the reruns do not end in the one error"
+    if m["error_step"] != fx.last + 1 or not 1 <= m["error_step"] <= scn["checkpoints"][-1]:
+        return "the error step is not the step after the last complete one"
+    if not at_limit(fx):
+        return "no bead at its limit after the last complete step"
+    if scn["twin"]:
+        tw = BY_NAME[scn["twin"]]
+        a, b = dict(scn["system"]), dict(tw["system"])
+        key = [k for k in ("extra_bond", "extra_special", "extra_angle") if a.get(k) != b.get(k)]
+        default = dict(extra_bond=1, extra_special=20, extra_angle=24)
+        if len(key) != 1 or b.get(key[0], default[key[0]]) != a[key[0]] + 1:
+            return "the twin is not one slot larger"
+        a.pop(key[0]), b.pop(key[0], None)
+        if a != b or script_for_steps(tw, 1) != script_for_steps(scn, 1):
+            return "the twin differs in more than the capacity"
+        if not any(p.startswith("full_") for p in tw["point"].split("+")):
+            return "the twin has no full row as its point"
+    return ""
 
 
 def fixture_conditions(fx):

@@ -153,3 +153,9 @@ def test_regenerated_fixtures_are_the_committed_ones(tmp_path):
         new = open(os.path.join(str(tmp_path), "ref_%s.npz" % name), "rb").read()
         assert new == open(os.path.join(rr.GOLDEN, "ref_%s.npz" % name), "rb").read(), name
         assert json.loads(json.dumps(meta)) == committed["scenarios"][name], name
+    # and one run that the reference aborts (test_reference_limits_cpu.py): error text, step and the state before it
+    name = "limit_load_angles"
+    meta = gen.make_limit(rr.LIMIT_BY_NAME[name], str(tmp_path), rr.load_melt, out=str(tmp_path))
+    new = open(os.path.join(str(tmp_path), "ref_%s.npz" % name), "rb").read()
+    assert new == open(os.path.join(rr.GOLDEN, "ref_%s.npz" % name), "rb").read(), name
+    assert json.loads(json.dumps(meta)) == committed["limits"][name], name
