@@ -10,6 +10,7 @@
 #include "../../include/lammps_le.h"
 #include "comm.h"
 #include "device.h"
+#include "soft_inl.h"
 
 namespace lmp_le { unsigned dd_halo_mismatches(DeviceState &d); }
 using namespace lmp_le;
@@ -649,8 +650,8 @@ static const std::vector<std::pair<std::string, std::vector<std::string>>> &styl
       {"bond", {"fene", "harmonic", "hybrid", "none", "zero"}},
       {"compute", {"pair/local", "property/local"}},
       {"dump", {"atom", "custom", "dcd", "local"}},
-      {"fix", {"bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve", "wall/region"}},
-      {"pair", {"lj/cut", "none", "zero"}},
+      {"fix", {"adapt", "bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve", "wall/region"}},
+      {"pair", {"lj/cut", "none", "soft", "zero"}},
   };
   return t;
 }
@@ -826,6 +827,8 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "steps_fused_thermo") return (double)e->steps_fused_thermo;
   if (k == "steps_unfused") return (double)e->steps_unfused;
   if (k == "steps_fused_wall") return (double)e->steps_fused_wall;      // of steps_fused: fix wall/region inside the step kernel
+  if (k == "steps_fused_soft") return (double)e->steps_fused_soft;      // of steps_fused: pair_style soft inside the step kernel
+  if (k == "pair_table_copies") return (double)e->pair_table_copies;    // fix adapt: copies of the pair table in the middle of runs
   if (k == "neigh_time" || k == "time_neigh") return e->timers[Engine::T_NEIGH];
   if (k == "time_pair") return e->timers[Engine::T_PAIR];
   if (k == "time_bond") return e->timers[Engine::T_BOND];
@@ -893,6 +896,50 @@ extern "C" int lammps_le_test_slab_rule(double prd_z, int world, double cutneigh
   const int code = (int)lmp_le::slab_rule(prd_z, world, cutneighmax, comm_cutoff, why);
   if (msg && cap > 0) { strncpy(msg, why.c_str(), (size_t)cap - 1); msg[cap - 1] = 0; }
   return code;
+}
+
+// test hooks (not part of the reference surface, not declared in include/lammps_le.h): the arithmetic of pair_style soft
+// (soft_inl.h) compiled for the host - the same functions, the same fma's the kernels run.  The sine and cosine on [0, pi] for n
+// arguments; the pair term for n squared distances with A and rc: fpair and energy without the special weight.  The host's
+// estimate of the reciprocal square root stands in for v_rsq_f64 (cut to 24 bits: the Newton steps must do the rest here too)
+extern "C" void lammps_le_test_soft_sincos(int n, const double *x, double *s, double *c) {
+  for (int i = 0; i < n; i++) { s[i] = lmp_le::soft_sin_0pi(x[i]); c[i] = lmp_le::soft_cos_0pi(x[i]); }
+}
+extern "C" void lammps_le_test_soft_pair(int n, const double *rsq, double a, double rc, double *fpair, double *evdwl) {
+  const double pi = 3.14159265358979323846;
+  const double a_pi_rc = a * pi / rc, pi_rc = pi / rc;          // the table columns as Engine::init_pair_coeffs derives them
+  for (int i = 0; i < n; i++) {
+    double seed = 1.0 / std::sqrt(rsq[i]);
+    if (seed < 3.0e38 && seed > 1.2e-38) seed = (double)(float)seed;      // (outside float's range: the estimate as it is)
+    double e = 0.0;
+    fpair[i] = lmp_le::soft_pair<true>(rsq[i], seed, a_pi_rc, pi_rc, a, e);
+    evdwl[i] = e;
+  }
+}
+
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): the derived pair coefficients as the
+// script layer holds them, without a device - what Engine::push_pair_table would send.  phase 0: after the init() of a run
+// command; 1: at the setup of a run over steps [begin, end] (fix adapt's setup_pre_force); 2: before the forces of step `now`
+// of that run (pre_force); 3: after the run (post_run).  out: 6 columns of (ntypes+1)^2 - cutsq lj1 lj2 lj3 lj4 offset, under
+// pair_style soft cutsq, A pi/rc, pi/rc, A, 0, 0.  Returns ntypes + 1, or -1 with the error recorded on the handle.
+extern "C" int lammps_le_test_pair_coeffs(void *handle, int phase, long begin, long end, long now, double *out) {
+  BEGIN_CAPTURE
+  struct InRun { Engine *e; bool was; long b0, e0, n0; InRun(Engine *en) : e(en), was(en->in_run), b0(en->beginstep), e0(en->endstep), n0(en->ntimestep) {}
+                 ~InRun() { e->in_run = was; e->beginstep = b0; e->endstep = e0; e->ntimestep = n0; } } keep(e);
+  if (phase == 0) e->init();
+  else {
+    e->in_run = true; e->beginstep = begin; e->endstep = end; e->ntimestep = phase == 1 ? begin : now;
+    if (phase == 1) e->adapt_set_values(true);
+    else if (phase == 2) e->adapt_set_values(false);
+    else e->adapt_restore_values();
+  }
+  const int nt = e->ntypes + 1;
+  const std::vector<double> *col[6] = {&e->cutsq, &e->lj1, &e->lj2, &e->lj3, &e->lj4, &e->offset};
+  for (int q = 0; q < 6; q++)
+    for (int k = 0; k < nt * nt; k++) out[(size_t)q * nt * nt + k] = (*col[q])[k];
+  return nt;
+  END_CAPTURE
+  return -1;
 }
 
 // test hook (not part of the reference surface, not declared in include/lammps_le.h): what all instances of this process

@@ -94,6 +94,7 @@ inline SlabRule slab_rule(double prd_z, int world, double cutneighmax, double co
 constexpr int CELL_XSPLIT = 4;
 
 constexpr int ANGLE_PACK_COLS = 4;
+constexpr int PAIRTAB_RING = 8;
 constexpr int LE_MAX_FIXES = 16;   // extrusion / ex_load / ex_unload / bond/create / bond/break instances with a device RanMars state each
 
 // The one owner of what an instance holds on the device: device blocks, pinned host blocks, streams and events.  A record
@@ -239,6 +240,12 @@ struct DeviceState {
   int sflag[4] = {1, 1, 1, 1};   // Engine::special_flag per level: 0 dropped from the list, 1 ordinary entry, 2 entry with level bits
   int pair_uniform = 0;      // every type pair has the same coefficients
   double pair_u[6] = {0, 0, 0, 0, 0, 0};
+  // fix adapt, runs whose kernels read the table: PAIRTAB_RING pinned copies of it, written in turn; pairtab_ev[k] is recorded
+  // behind the copy out of row k, and row k is written again only after that event (it passed long ago: the ring is deeper
+  // than the host ever runs ahead of the stream between two waits of its own)
+  double *pairtab_ring = nullptr;
+  hipEvent_t pairtab_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int pairtab_next = 0;
   double cutneigh = 0.0;
   // ---- thermo partial sums ----
   int nred_blocks = 0;
@@ -382,7 +389,7 @@ void dev_alloc_neigh(DeviceState &d, int maxneigh);
 
 // integrate (kernels_md.hip)
 void launch_initial_integrate(DeviceState &d, const TypeTables &tt, double dtv, double triggersq, bool check, int groupbit = 1);
-void launch_force(DeviceState &d, const BondTable &bt, const double special_lj[4], bool eflag, bool has_pair, int parts = 3);
+void launch_force(DeviceState &d, const BondTable &bt, const double special_lj[4], bool eflag, bool has_pair, int parts = 3, bool soft = false);
 void launch_flevel_copy(DeviceState &d, double *flevel, bool to_level, bool add);
 // the fused step kernel: the variant `plan` names (step_plan.h), fused force + Langevin + final_integrate [+ the next
 // initial_integrate]; what a launch needs beyond the plan and the device state:

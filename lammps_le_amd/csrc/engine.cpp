@@ -98,10 +98,46 @@ void Engine::init() {
     if (!mass_set[t]) throw LammpsError("Not all per-type masses are set");
   if (ntypes > MAXTYPES || nbondtypes > MAXTYPES)
     throw LammpsError("MI355X engine handles at most " + std::to_string(MAXTYPES) + " atom/bond types");
+  init_pair_coeffs();
+  cutneighmax = (pair_lj || pair_zero || pair_soft) ? cutforcemax + skin : 0.0;
+  if (atom_style != "atomic" && !bond_style_name.empty() && bond_style_name != "zero" && bond_style_name != "none")
+    for (int b = 1; b <= nbondtypes; b++)
+      if (bondtab.style[b] == 0 && nbonds > 0) throw LammpsError("All bond coeffs are not set");
+  if (!special_built) build_special();
+  for (auto &f : fixes) f->init();
+  init_local_computes();
+}
+
+// Pair::init -> init_one for every type pair (src/pair.cpp:190-260, src/pair_lj_cut.cpp:512-569, src/pair_soft.cpp:200-213); also
+// what Pair::reinit does after fix adapt changed a coefficient (src/pair.cpp:262-275): unset pairs are mixed again from the
+// diagonal as it stands now
+void Engine::init_pair_coeffs() {
   int nt = ntypes + 1;
   lj1.assign(nt * nt, 0.0); lj2 = lj3 = lj4 = offset = cutsq = lj1;
   cutforcemax = 0.0;
-  if (pair_lj) {
+  if (pair_soft) {
+    if ((int)pc_set.size() != nt * nt) throw LammpsError("All pair coeffs are not set");
+    for (int i = 1; i <= ntypes; i++)
+      if (!pc_set[i * nt + i]) throw LammpsError("All pair coeffs are not set");
+    const double pi = 3.14159265358979323846;      // MY_PI
+    for (int i = 1; i <= ntypes; i++)
+      for (int j = i; j <= ntypes; j++) {
+        int ij = i * nt + j, ji = j * nt + i, ii = i * nt + i, jj = j * nt + j;
+        double a, cut;
+        if (pc_set[ij]) { a = pc_eps[ij]; cut = pc_cut[ij]; }
+        else {    // prefactors always mix geometrically, cutoffs by pair_modify mix (mix_distance)
+          a = std::sqrt(pc_eps[ii] * pc_eps[jj]);
+          cut = pair_mix ? 0.5 * (pc_cut[ii] + pc_cut[jj]) : std::sqrt(pc_cut[ii] * pc_cut[jj]);
+        }
+        cutsq[ij] = cut * cut;
+        lj1[ij] = a * pi / cut;      // A pi / rc
+        lj2[ij] = pi / cut;
+        lj3[ij] = a;
+        lj1[ji] = lj1[ij]; lj2[ji] = lj2[ij]; lj3[ji] = lj3[ij]; cutsq[ji] = cutsq[ij];
+        cutforcemax = std::max(cutforcemax, cut);
+      }
+  } else if (pair_lj) {
+    if ((int)pc_set.size() != nt * nt) throw LammpsError("All pair coeffs are not set");
     for (int i = 1; i <= ntypes; i++)
       if (!pc_set[i * nt + i]) throw LammpsError("All pair coeffs are not set");
     for (int i = 1; i <= ntypes; i++)
@@ -128,13 +164,53 @@ void Engine::init() {
         cutforcemax = std::max(cutforcemax, cut);
       }
   } else if (pair_zero) cutforcemax = pair_cut_global;
-  cutneighmax = (pair_lj || pair_zero) ? cutforcemax + skin : 0.0;
-  if (atom_style != "atomic" && !bond_style_name.empty() && bond_style_name != "zero" && bond_style_name != "none")
-    for (int b = 1; b <= nbondtypes; b++)
-      if (bondtab.style[b] == 0 && nbonds > 0) throw LammpsError("All bond coeffs are not set");
-  if (!special_built) build_special();
-  for (auto &f : fixes) f->init();
-  init_local_computes();
+}
+
+// The pair table of the force kernels (6 columns of (ntypes+1)^2: cutsq lj1 lj2 lj3 lj4 offset, or soft's cutsq, A pi/rc, pi/rc,
+// A, 0, 0) and, when every type pair has the same row, the scalars that stand for it.  Called by upload(), by run() (the style
+// or a coefficient may have changed on a handle whose atoms are already on the device) and by fix adapt in the middle of a run.
+// There the scalars of the next launch carry the new values at no cost - they are kernel arguments -, and the table is copied
+// only when the kernels read it (several coefficient sets, or list entries with special bits), from one of PAIRTAB_RING pinned
+// rows, on the run's stream, so that it lands between the launch of the step before and the launch of this step.  No host wait
+// (the event of a row has long passed when the row comes round again) and no allocation per step.
+void Engine::push_pair_table(bool mid_run) {
+  DeviceState &d = *dev;
+  const int ntp = ntypes + 1;
+  const size_t words = 6 * (size_t)ntp * ntp;
+  if (!d.pairtab_ring) {
+    d.mem.alloc_host(d.pairtab_ring, (size_t)PAIRTAB_RING * 6 * (MAXTYPES + 1) * (MAXTYPES + 1), "d.pairtab_ring");
+    for (int k = 0; k < PAIRTAB_RING; k++) d.mem.event(d.pairtab_ev[k], "d.pairtab_ev[k]", hipEventDisableTiming);
+    d.pairtab_next = 0;
+  }
+  const int slot = d.pairtab_next;
+  double *tab = d.pairtab_ring + (size_t)slot * 6 * (MAXTYPES + 1) * (MAXTYPES + 1);
+  const bool force = pair_force();
+  bool uniform = force;
+  double u[6] = {0, 0, 0, 0, 0, 0};
+  const std::vector<double> *col[6] = {&cutsq, &lj1, &lj2, &lj3, &lj4, &offset};
+  if (force) {
+    const int ref = 1 * ntp + 1;
+    for (int q = 0; q < 6; q++) u[q] = (*col[q])[ref];
+    for (int i = 1; i <= ntypes && uniform; i++)
+      for (int j = 1; j <= ntypes; j++)
+        for (int q = 0; q < 6; q++)
+          if ((*col[q])[i * ntp + j] != u[q]) uniform = false;
+  }
+  bool has_sb = false;
+  for (int k = 1; k <= 3; k++) if (special_flag(k) == 2) has_sb = true;
+  d.pair_uniform = uniform ? 1 : 0;
+  for (int q = 0; q < 6; q++) d.pair_u[q] = u[q];
+  // the force kernels of this run read the scalars only; whoever else reads the table (the pair rows of the local computes,
+  // kernels_local.hip) asks for it first, and so does the end of the run (pair_table_stale)
+  if (mid_run && uniform && !has_sb) { pair_table_stale = true; return; }
+  pair_table_stale = false;
+  HIP_CHECK(hipEventSynchronize(d.pairtab_ev[slot]));
+  for (int q = 0; q < 6; q++)
+    for (int k = 0; k < ntp * ntp; k++) tab[(size_t)q * ntp * ntp + k] = force ? (*col[q])[k] : 0.0;
+  HIP_CHECK(hipMemcpyAsync(d.pairtab, tab, words * sizeof(double), hipMemcpyHostToDevice, d.stream));
+  HIP_CHECK(hipEventRecord(d.pairtab_ev[slot], d.stream));
+  d.pairtab_next = (slot + 1) % PAIRTAB_RING;
+  if (mid_run) pair_table_copies++;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -296,24 +372,8 @@ void Engine::upload() {
       up(dst[q], ag[q].data(), nt * apa * sizeof(int));
     }
   }
-  int ntp = ntypes + 1;
-  std::vector<double> tab(6 * (size_t)ntp * ntp, 0.0);
-  if (pair_lj)
-    for (int k = 0; k < ntp * ntp; k++) {
-      tab[k] = cutsq[k]; tab[ntp * ntp + k] = lj1[k]; tab[2 * ntp * ntp + k] = lj2[k];
-      tab[3 * ntp * ntp + k] = lj3[k]; tab[4 * ntp * ntp + k] = lj4[k]; tab[5 * ntp * ntp + k] = offset[k];
-    }
-  up(d.pairtab, tab.data(), tab.size() * sizeof(double));
-  d.pair_uniform = pair_lj ? 1 : 0;
+  push_pair_table(false);
   d.cutneigh = cutneighmax + skin;   // interior test margin: listed at build (within cutneigh) + drift since then
-  if (pair_lj) {
-    int ref = 1 * ntp + 1;
-    for (int i = 1; i <= ntypes; i++)
-      for (int j = 1; j <= ntypes; j++)
-        for (int q = 0; q < 6; q++)
-          if (tab[(size_t)q * ntp * ntp + i * ntp + j] != tab[(size_t)q * ntp * ntp + ref]) d.pair_uniform = 0;
-    for (int q = 0; q < 6; q++) d.pair_u[q] = tab[(size_t)q * ntp * ntp + ref];
-  }
   HIP_CHECK(hipMemsetAsync(d.flags, 0, NFLAGS * sizeof(int), d.stream));
   {
     // special lists that disagree between the two ends of a pair (possible after an ex_unload acted on a stale
@@ -490,7 +550,7 @@ RebuildFacts Engine::rebuild_facts(bool can_defer, bool sort_due, bool regrow, b
   f.bond_minimg = d.bond_minimg != 0; f.bpa = d.bpa; f.bond_pack_stride = d.bond_pack_stride; f.bpart = d.bpart != nullptr;
   // (`pair_style zero` builds the pair list like any pair style - that is what the style is for, src/pair_zero.cpp - although
   //  no force kernel reads its pair entries: without a pair force they take the bonds from the bond-partner table)
-  f.pair = pair_lj || pair_zero;
+  f.pair = pair_lj || pair_zero || pair_soft;
   for (int k = 1; k <= 3; k++) f.sf[k] = d.sflag[k];
   f.special_asym = d.flags_h[FLAG_SPECIAL_ASYM] != 0;
   f.row_tile = d.row_tile;
@@ -711,7 +771,7 @@ bool Engine::angles_active() const {
   return false;
 }
 void Engine::compute_forces(bool eflag) {
-  launch_force(*dev, bondtab, special_lj, eflag, pair_lj);
+  launch_force(*dev, bondtab, special_lj, eflag, pair_force(), 3, pair_soft);
   if (angles_active()) launch_angle(*dev, angtab, eflag);     // Angle::compute follows Bond::compute (src/verlet.cpp:298-302)
 }
 
@@ -736,7 +796,7 @@ const Engine::PairRows &Engine::pair_rows(const LocalCompute &c) {
   static const char *stale = "Compute used in dump between runs is not current";
   const int kind = c.kind, bit = c.bit;
   init_local_compute(c);         // (a compute defined since the last run has not seen its init() checks yet)
-  if (!(pair_lj || pair_zero)) throw LammpsError("No pair style is defined for compute " + c.style);      // (no list without one)
+  if (!(pair_lj || pair_zero || pair_soft)) throw LammpsError("No pair style is defined for compute " + c.style);      // (no list without one)
   if (!dev || !dev_current || !dev->pos || !dev->neigh || reneigh_pending || !pair_list_ready) throw LammpsError(stale);
   if (world > 1 && dev_edits != dev_edits_at_run) throw LammpsError(stale);      // (ghost copies of a moved bead are not refreshed)
   for (auto &r : pair_rows_cache)
@@ -755,10 +815,11 @@ const Engine::PairRows &Engine::pair_rows(const LocalCompute &c) {
     gmask_uploaded_version = group_version;
   }
   LocalRowsRequest rq;
-  rq.pair = kind == LOCAL_PAIR; rq.bit = bit; rq.zero = !pair_lj; rq.zero_cutsq = pair_cut_global * pair_cut_global;
+  rq.pair = kind == LOCAL_PAIR; rq.bit = bit; rq.zero = pair_zero; rq.zero_cutsq = pair_cut_global * pair_cut_global;
   for (int k = 0; k < 4; k++) rq.special_lj[k] = special_lj[k];
   const int *ids = nullptr;
   const double *vals = nullptr;
+  if (pair_table_stale) push_pair_table(false);      // fix adapt changed coefficients that travelled as scalars: the rows read the table
   const long mine = local_pair_rows(d, rq, ids, vals, pair_rows_ms);
   PairRows *out = nullptr;
   for (auto &r : pair_rows_cache) if (r.kind == kind && r.bit == bit) out = &r;
@@ -876,6 +937,60 @@ static int walls_request(const Engine *e) {      // StepRequest::walls
 static bool walls_behind_langevin(const Engine *e) {
   for (int k = 0; k < e->walltab.n; k++) if (e->walltab.w[k].after_langevin) return true;
   return false;
+}
+
+// fix adapt (src/fix_adapt.cpp:495-515, :536-665): at setup of a run every fix adapt sets its values, in the loop those whose
+// step it is; then Pair::reinit - every type pair derived again, mixing included - and the new coefficients go to the device
+// (push_pair_table).  The formulas are evaluated on the host between two launches, so they may read nothing that lives on the
+// device (Parser: host_only_for)
+bool Engine::have_adapt() const {
+  for (auto &f : fixes) if (dynamic_cast<FixAdapt *>(f.get())) return true;
+  return false;
+}
+void Engine::adapt_apply(bool at_setup) {
+  if (adapt_set_values(at_setup)) push_pair_table(true);
+}
+bool Engine::adapt_set_values(bool at_setup) {
+  bool any = false;
+  const int nt = ntypes + 1;
+  for (auto &f : fixes) {
+    auto *fa = dynamic_cast<FixAdapt *>(f.get());
+    if (!fa) continue;
+    if (!at_setup && (fa->nevery == 0 || ntimestep % fa->nevery)) continue;
+    for (auto &c : fa->clauses) {
+      double value;
+      host_only_for = c.var;
+      try { value = variable_value(c.var); } catch (...) { host_only_for.clear(); throw; }
+      host_only_for.clear();
+      std::vector<double> &arr = *fa->target(c);
+      for (int i = c.ilo; i <= c.ihi; i++)
+        for (int j = std::max(c.jlo, i); j <= c.jhi; j++)
+          arr[i * nt + j] = fa->scaleflag ? value * c.orig[i * nt + j] : value;
+      any = true;
+    }
+  }
+  if (any) init_pair_coeffs();
+  return any;
+}
+void Engine::adapt_post_run() {
+  if (adapt_restore_values() || pair_table_stale) push_pair_table(false);      // between runs the table holds what the script layer holds
+}
+bool Engine::adapt_restore_values() {
+  bool any = false;
+  const int nt = ntypes + 1;
+  for (auto &f : fixes) {
+    auto *fa = dynamic_cast<FixAdapt *>(f.get());
+    if (!fa || !fa->resetflag) continue;
+    for (auto &c : fa->clauses) {
+      std::vector<double> &arr = *fa->target(c);
+      if (c.orig.size() != arr.size()) continue;
+      for (int i = c.ilo; i <= c.ihi; i++)
+        for (int j = std::max(c.jlo, i); j <= c.jhi; j++) arr[i * nt + j] = c.orig[i * nt + j];
+      any = true;
+    }
+  }
+  if (any) init_pair_coeffs();
+  return any;
 }
 
 ThermoRow Engine::eval_thermo(bool ke_summed) {
@@ -1055,7 +1170,8 @@ void Engine::setup() {
   double s1 = wall();
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = 0;
+  adapt_apply(true);                              // FixAdapt::setup_pre_force
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
@@ -1097,10 +1213,11 @@ void Engine::iterate(long nsteps) {
   const bool ang = angles_active();
   if (ang && fusable) upload_angle_table(d, angtab);
   StepRequest rq;
-  rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_lj; rq.angles = ang;
+  rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_force(); rq.soft = pair_soft; rq.angles = ang;
   rq.nvebit = fusable ? nbits[0] : 1; rq.lgbit = lg ? lg->groupbit : 1;
   rq.walls = walls_request(this);
   bool pre_integrated = false;
+  const bool adapting = have_adapt();
   // halo/compute overlap issues the per-step halo on a second stream.  With RCCL that means two streams feeding ONE
   // communicator (ordered by events, but never run on multi-GPU hardware): kept to the test transports unless
   // LAMMPS_LE_OVERLAP_RCCL=1 says otherwise
@@ -1147,6 +1264,7 @@ void Engine::iterate(long nsteps) {
       stamp(T_COMM);
     }
     stamp();
+    if (adapting) adapt_apply(false);      // FixAdapt::pre_force: behind the rebuild, in front of this step's forces
     // (the rebuild may have moved beads between the ranks, and the displacement test counts from it)
     rq.check = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
     rq.cells = d.cell_count && d.ncells > 0;
@@ -1196,6 +1314,7 @@ void Engine::iterate(long nsteps) {
       steps_fused++;
       if (plan.grp) steps_fused_group++;
       if (plan.wall) steps_fused_wall++;
+      if (plan.soft) steps_fused_soft++;
       stamp(T_PAIR);          // the fused kernel: pair + bond + post_force + final_integrate (+ next initial_integrate)
     } else if (plan.fused) {
       // a thermo step without dumps: the step kernel's energy variant - forces, energies, virial, post_force and
@@ -1255,7 +1374,7 @@ static TypeTables level_tables(Engine *e, double step) {      // FixNVE::*_integ
 }
 void Engine::respa_level_forces(int l) {                       // Respa::recurse, force part (:664-713): pair, then bond
   const int parts = (respa_level_pair == l ? 1 : 0) | (respa_level_bond == l ? 2 : 0);
-  launch_force(*dev, bondtab, special_lj, false, pair_lj, parts);
+  launch_force(*dev, bondtab, special_lj, false, pair_force(), parts, pair_soft);
   if (respa_level_angle == l && angles_active()) launch_angle(*dev, angtab, false);      // (:707-710: behind the level's bonds)
 }
 void Engine::respa_setup() {                                   // Respa::setup (:369-468)
@@ -1271,8 +1390,9 @@ void Engine::respa_setup() {                                   // Respa::setup (
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = 0;
   for (int l = 0; l <= top; l++) {
+    if (l == top) adapt_apply(true);           // FixAdapt::setup_pre_force_respa: the outermost level only
     respa_level_forces(l);
     launch_flevel_copy(d, d.respa_flevel[l], true, false);
   }
@@ -1331,6 +1451,7 @@ void Engine::respa_recurse(int l, bool last) {
     }
     if (l) respa_recurse(l - 1, last_here);
     stamp();
+    if (l == top && have_adapt()) adapt_apply(false);      // FixAdapt::pre_force_respa (src/respa.cpp:675-677): outermost level
     respa_level_forces(l);
     stamp(T_PAIR);
     // post_force_respa at the outermost level (src/fix_langevin.cpp:576-579, src/fix_wall_region.cpp:306-309), in fix order; a
@@ -1421,7 +1542,13 @@ void Engine::run(long nsteps) {
   // (the fixes on groups are not those of the last upload: the masks, the member ranks and the thermostat's member count travel
   // with an upload - also when the last fix on a group has gone and they have to fall back to `all`)
   if (dev && dev_current && group_sig != group_signature()) { download(); dev_current = false; }
+  // (so are the cell grid and the lists for the cutoff of the last upload: another pair style or cutoff on the same handle)
+  char psig[96];
+  snprintf(psig, sizeof psig, "%s %.17g", pair_style_name(), cutneighmax);
+  if (dev && dev_current && pair_sig != psig) { download(); dev_current = false; }
+  pair_sig = psig;
   if (!dev_current || !dev || !dev->pos) upload();
+  else push_pair_table(false);       // coefficients given since the last run
   group_sig = group_signature();
   build_wall_table();
   // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
@@ -1464,6 +1591,7 @@ void Engine::run(long nsteps) {
   halo_step = -1;
   host_current = false;
   double t0 = 0.0;
+  struct InRun { bool &f; InRun(bool &b) : f(b) { f = true; } ~InRun() { f = false; } } in_run_guard(in_run);
   try {
     if (respa_levels > 0) respa_setup(); else setup();
     for (int k = 0; k < 8; k++) timers[k] = 0.0;     // Timer::init() comes after setup (src/run.cpp:176-181)
@@ -1477,6 +1605,7 @@ void Engine::run(long nsteps) {
     atime += (double)(ntimestep - atimestep) * dt;       // Update::update_time at the end of a run (src/verlet.cpp:362)
     atimestep = ntimestep;
     dev_edits_at_run = dev_edits;
+    adapt_post_run();                                    // FixAdapt::post_run: reset yes
   } catch (...) {
     // a rank that leaves the loop on an error must not keep its peers inside a collective: tear the communicator down
     // (they end with "communicator aborted" or their own copy of the error; see Comm::wait_stream)

@@ -217,6 +217,23 @@ struct FixWallRegion : Fix {
   bool extensive() const override { return true; }       // (src/fix_wall_region.cpp:45-46)
 };
 
+// fix ID group adapt N pair soft a | lj/cut epsilon | lj/cut sigma I J v_name [pair ...] [reset yes|no] [scale yes|no]
+// (src/fix_adapt.cpp).  Holds the script's words; the values are set by Engine::adapt_apply at setup of every run and before the
+// force evaluation of every step with step % N == 0, and travel to the device as Engine::push_pair_table describes
+struct FixAdapt : Fix {
+  struct Clause {
+    std::string pstyle, pparam, var;
+    int ilo, ihi, jlo, jhi;
+    std::vector<double> orig;        // [(ntypes+1)^2] the parameter as FixAdapt::init found it (array_orig)
+  };
+  int nevery = 0;
+  bool resetflag = false, scaleflag = false;
+  std::vector<Clause> clauses;
+  FixAdapt(Engine *e, const std::vector<std::string> &arg);
+  void init() override;              // the checks of FixAdapt::init (:316-491) and the copy of the original values
+  std::vector<double> *target(const Clause &c) const;   // the array of Engine the clause sets (pc_eps | pc_sig)
+};
+
 // ---------------------------------------------------------------------------------------------
 // Engine = the LAMMPS instance behind one C-API handle
 // ---------------------------------------------------------------------------------------------
@@ -295,6 +312,28 @@ class Engine {
 
   // ---- styles ----
   bool pair_lj = false, pair_zero = false;
+  // pair_style soft (src/pair_soft.cpp): A lives in pc_eps, rc in pc_cut; the derived columns lj1 lj2 lj3 then hold A pi/rc, pi/rc
+  // and A (soft_inl.h), lj4 and offset stay 0
+  bool pair_soft = false;
+  bool pair_force() const { return pair_lj || pair_soft; }       // a pair style that computes something
+  const char *pair_style_name() const { return pair_lj ? "lj/cut" : pair_soft ? "soft" : pair_zero ? "zero" : "none"; }
+  void init_pair_coeffs();          // Pair::init / Pair::reinit: every type pair's derived coefficients, mixing included
+  // the table and the scalars of the force kernels from the derived coefficients.  The scalars are refreshed; the table is
+  // copied on the run's stream from a ring of pinned rows that stay untouched until the copy has run - except `mid_run` (fix
+  // adapt between two launches) when the force kernels read the scalars alone: then the copy is left out and pair_table_stale
+  // says so, until someone who reads the table (Engine::pair_rows) or the end of the run asks for it
+  void push_pair_table(bool mid_run);
+  bool pair_table_stale = false;
+  long steps_fused_soft = 0;        // of steps_fused: the step kernel's soft variant
+  long pair_table_copies = 0;       // mid-run copies of the pair table by fix adapt (lammps_le_stat "pair_table_copies")
+  std::string pair_sig;             // pair style and neighbor cutoff of the last upload
+  bool in_run = false;              // Update::whichflag != 0: ramp() is legal
+  std::string host_only_for;        // != "": a formula evaluated for this fix adapt variable must not read the device
+  void adapt_apply(bool setup);     // FixAdapt::setup_pre_force / pre_force of every fix adapt, then Pair::reinit + push
+  void adapt_post_run();            // FixAdapt::post_run: reset yes
+  bool adapt_set_values(bool setup);   // the host part of adapt_apply: true when a coefficient was set (and all derived again)
+  bool adapt_restore_values();         // ... of adapt_post_run
+  bool have_adapt() const;
   double pair_cut_global = 0.0;
   bool pair_shift = false;
   int pair_mix = 0;  // 0 geometric, 1 arithmetic
@@ -531,5 +570,6 @@ class Engine {
 double numeric(const std::string &s);
 int inumeric(const std::string &s);
 std::vector<std::string> split_words(const std::string &line);
+void bounds(const std::string &s, int nmax, int &lo, int &hi);   // "*", "n*", "*m", "n*m" type ranges (src/utils.cpp bounds)
 
 }  // namespace lmp_le

@@ -72,6 +72,68 @@ FixLangevin::FixLangevin(Engine *e, const std::vector<std::string> &arg) {
   has_post_force = true;
 }
 
+// fix ID group adapt N pair pstyle pparam I J v_name ... [reset yes|no] [scale yes|no]  (src/fix_adapt.cpp:45-215).  Pair
+// parameters only, and of those the ones PairSoft::extract and PairLJCut::extract expose: soft a, lj/cut epsilon, lj/cut sigma.
+// The group is parsed and, as in the reference, not used for pair parameters.
+FixAdapt::FixAdapt(Engine *e, const std::vector<std::string> &arg) {
+  eng = e; id = arg[0]; group = arg[1]; style = arg[2];
+  const char *ill = "Illegal fix adapt command";
+  if (arg.size() < 5) throw LammpsError(ill);
+  groupbit = fix_group(e, arg);
+  nevery = inumeric(arg[3]);
+  if (nevery < 0) throw LammpsError(ill);
+  size_t k = 4;
+  while (k < arg.size()) {
+    if (arg[k] == "pair") {
+      if (k + 6 > arg.size()) throw LammpsError(ill);
+      Clause c;
+      c.pstyle = arg[k + 1]; c.pparam = arg[k + 2];
+      bounds(arg[k + 3], e->ntypes, c.ilo, c.ihi);
+      bounds(arg[k + 4], e->ntypes, c.jlo, c.jhi);
+      if (arg[k + 5].rfind("v_", 0) != 0) throw LammpsError(ill);
+      c.var = arg[k + 5].substr(2);
+      if (c.pstyle != "soft" && c.pstyle != "lj/cut")
+        throw LammpsError("MI355X engine: fix adapt pair style " + c.pstyle + " is not supported (soft a, lj/cut epsilon, lj/cut sigma)");
+      if (!((c.pstyle == "soft" && c.pparam == "a") || (c.pstyle == "lj/cut" && (c.pparam == "epsilon" || c.pparam == "sigma"))))
+        throw LammpsError("MI355X engine: Fix adapt pair style param not supported: " + c.pstyle + " " + c.pparam);
+      clauses.push_back(c);
+      k += 6;
+    } else if (arg[k] == "bond" || arg[k] == "kspace" || arg[k] == "atom") {
+      const size_t n = arg[k] == "bond" ? 5 : arg[k] == "kspace" ? 2 : 3;
+      if (k + n > arg.size()) throw LammpsError(ill);
+      throw LammpsError("MI355X engine: fix adapt " + arg[k] + " is not supported (pair soft a, pair lj/cut epsilon | sigma)");
+    } else break;
+  }
+  if (clauses.empty()) throw LammpsError(ill);
+  for (; k < arg.size(); k += 2) {
+    if (k + 2 > arg.size()) throw LammpsError(ill);
+    const std::string &kw = arg[k], &val = arg[k + 1];
+    if (val != "yes" && val != "no") throw LammpsError(ill);
+    if (kw == "reset") resetflag = val == "yes";
+    else if (kw == "scale") scaleflag = val == "yes";
+    else if (kw == "mass") {}                    // (atom diameter only)
+    else throw LammpsError(ill);
+  }
+}
+std::vector<double> *FixAdapt::target(const Clause &c) const { return c.pparam == "sigma" ? &eng->pc_sig : &eng->pc_eps; }
+void FixAdapt::init() {
+  const int nt = eng->ntypes + 1;
+  for (auto &c : clauses) {
+    auto vi = eng->var_info.find(c.var);
+    if (eng->variables.find(c.var) == eng->variables.end()) throw LammpsError("Variable name for fix adapt does not exist");
+    if (vi == eng->var_info.end() || vi->second.style != "equal") throw LammpsError("Variable for fix adapt is invalid style");
+    if (c.pstyle != eng->pair_style_name()) throw LammpsError("Fix adapt pair style does not exist");
+    const std::vector<double> &arr = *target(c);
+    if ((int)arr.size() != nt * nt) throw LammpsError("All pair coeffs are not set");
+    c.orig = arr;                                // (array_orig: the values as this run finds them, :460-466)
+    // the formula is evaluated on the host between two launches of a run: one that reads an energy, a temperature, the
+    // pressure or a fix is refused here, at the run command, with the name of what it reads (Parser, input.cpp)
+    struct Dry { Engine *e; bool was; Dry(Engine *en, const std::string &v) : e(en), was(en->in_run) { e->in_run = true; e->host_only_for = v; }
+                 ~Dry() { e->in_run = was; e->host_only_for.clear(); } } dry(eng, c.var);
+    (void)eng->variable_value(c.var);
+  }
+}
+
 // fix ID group wall/region region-ID style args cutoff  (src/fix_wall_region.cpp:35-92): lj93 | lj126 | lj1043 | harmonic take
 // epsilon sigma cutoff, morse takes D0 alpha r0 cutoff
 FixWallRegion::FixWallRegion(Engine *e, const std::vector<std::string> &arg) {
@@ -251,7 +313,7 @@ FixExLoad::FixExLoad(Engine *e, const std::vector<std::string> &arg) {
 }
 void FixExLoad::init() {
   // src/USER-LE/fix_ex_load.cpp:217-218
-  if (!eng->pair_lj) throw LammpsError("Fix " + style + " cutoff is longer than pairwise cutoff");
+  if (!eng->pair_force()) throw LammpsError("Fix " + style + " cutoff is longer than pairwise cutoff");      // (force->pair == nullptr)
   int nt = eng->ntypes + 1;
   if (cutsq > eng->cutsq[iatomtype * nt + jatomtype])
     throw LammpsError("Fix " + style + " cutoff is longer than pairwise cutoff");

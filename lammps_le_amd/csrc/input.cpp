@@ -52,7 +52,7 @@ std::vector<std::string> split_words(const std::string &line) {
 
 // ---------------------------------------------------------------------------------------------
 // formulas (src/variable.cpp Variable::evaluate, the subset a bead-spring script uses): numbers, + - * / % ^, unary -,
-// comparisons and && || !, parentheses, sqrt exp ln log abs sin cos tan floor ceil round min max, thermo keywords
+// comparisons and && || !, parentheses, sqrt exp ln log abs sin cos tan floor ceil round min max ramp, thermo keywords
 // (step dt atoms bonds vol temp press pe ke etotal epair emol), v_name, f_ID[k]
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -107,6 +107,9 @@ struct Parser {
     i = j;
     if (name.rfind("v_", 0) == 0) return e->variable_value(name.substr(2));
     if (name.rfind("f_", 0) == 0) {
+      if (!e->host_only_for.empty())
+        throw LammpsError("MI355X engine: variable " + e->host_only_for + " of fix adapt reads " + name +
+                          ", which lives on the device (numbers, step, elapsed, dt, time, ramp() and the math functions are evaluated per step)");
       int idx = 1;
       bool indexed = false;
       if (i < s.size() && s[i] == '[') { size_t k = s.find(']', i); if (k == std::string::npos) bad(); idx = atoi(s.c_str() + i + 1); i = k + 1; indexed = true; }
@@ -137,9 +140,30 @@ struct Parser {
       if (name == "round") return (double)llround(a);
       if (name == "min" && two) return a < b ? a : b;
       if (name == "max" && two) return a > b ? a : b;
+      if (name == "ramp" && two) {        // src/variable.cpp:3576-3588
+        if (!e->in_run) throw LammpsError("Cannot use ramp in variable formula between runs");
+        double delta = (double)(e->ntimestep - e->beginstep);
+        if (delta != 0.0) delta /= (double)(e->endstep - e->beginstep);
+        return a + delta * (b - a);
+      }
       throw LammpsError("Invalid math function in variable formula: " + name);
     }
     if (name == "step") return (double)e->ntimestep;
+    if (!e->host_only_for.empty()) {
+      // a formula fix adapt evaluates between two launches: what the host knows without a reduction on the device
+      if (name == "elapsed" || name == "elaplong") return (double)(e->ntimestep - e->beginstep);
+      if (name == "dt") return e->dt;
+      if (name == "time") return e->atime + (double)(e->ntimestep - e->atimestep) * e->dt;
+      if (name == "PI") return 3.14159265358979323846;
+      double val;
+      bool isint;
+      if (name == "atoms" || name == "bonds" || name == "angles" || name == "vol" || name == "lx" || name == "ly" || name == "lz") {
+        e->thermo_keyword(e->last_thermo, name, val, isint);
+        return val;
+      }
+      throw LammpsError("MI355X engine: variable " + e->host_only_for + " of fix adapt reads " + name +
+                        ", which lives on the device (numbers, step, elapsed, dt, time, ramp() and the math functions are evaluated per step)");
+    }
     {
       double val;
       bool isint;
@@ -287,7 +311,7 @@ static void set_units(Engine *e, const std::string &u) {
 }
 
 // expand "*", "n*", "*m", "n*m" type ranges (src/utils.cpp bounds)
-static void bounds(const std::string &s, int nmax, int &lo, int &hi) {
+void bounds(const std::string &s, int nmax, int &lo, int &hi) {
   size_t star = s.find('*');
   if (star == std::string::npos) { lo = hi = inumeric(s); }
   else {
@@ -472,8 +496,12 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     }
   } else if (cmd == "pair_style") {
     need(1);
-    pair_lj = pair_zero = false;
-    if (arg[0] == "lj/cut") {
+    pair_lj = pair_zero = pair_soft = false;
+    if (arg[0] == "soft") {
+      if (arg.size() != 2) throw LammpsError("Illegal pair_style command");      // src/pair_soft.cpp:150
+      pair_soft = true;
+      pair_cut_global = numeric(arg[1]);
+    } else if (arg[0] == "lj/cut") {
       need(2);
       pair_lj = true;
       pair_cut_global = numeric(arg[1]);
@@ -502,8 +530,26 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
   } else if (cmd == "pair_coeff") {
     // i j epsilon sigma [cut]  (src/pair_lj_cut.cpp:446-474)
     if (!box_exist) throw LammpsError("Pair_coeff command before simulation box is defined");
-    if (!pair_lj && !pair_zero) throw LammpsError("Pair_coeff command before pair_style is defined");
+    if (!pair_lj && !pair_zero && !pair_soft) throw LammpsError("Pair_coeff command before pair_style is defined");
     if (pair_zero) return;
+    if (pair_soft) {
+      // i j A [rc]  (src/pair_soft.cpp:168-194)
+      if (arg.size() < 3 || arg.size() > 4) throw LammpsError("Incorrect args for pair coefficients");
+      int ilo, ihi, jlo, jhi;
+      bounds(arg[0], ntypes, ilo, ihi);
+      bounds(arg[1], ntypes, jlo, jhi);
+      const double a = numeric(arg[2]);
+      const double cut = (arg.size() == 4) ? numeric(arg[3]) : pair_cut_global;
+      int nt = ntypes + 1, count = 0;
+      if ((int)pc_set.size() != nt * nt) { pc_eps.assign(nt * nt, 0.0); pc_sig = pc_cut = pc_eps; pc_set.assign(nt * nt, 0); }
+      for (int i = ilo; i <= ihi; i++)
+        for (int j = std::max(jlo, i); j <= jhi; j++) {
+          pc_eps[i * nt + j] = a; pc_sig[i * nt + j] = 0.0; pc_cut[i * nt + j] = cut; pc_set[i * nt + j] = 1;
+          count++;
+        }
+      if (count == 0) throw LammpsError("Incorrect args for pair coefficients");
+      return;
+    }
     if (arg.size() < 4 || arg.size() > 5) throw LammpsError("Incorrect args for pair coefficients");
     int ilo, ihi, jlo, jhi;
     bounds(arg[0], ntypes, ilo, ihi);
@@ -530,6 +576,7 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     else if (st == "extrusion") f.reset(new FixExtrusion(this, arg));
     else if (st == "ex_load" || st == "bond/create") f.reset(new FixExLoad(this, arg));
     else if (st == "ex_unload" || st == "bond/break") f.reset(new FixExUnload(this, arg));
+    else if (st == "adapt") f.reset(new FixAdapt(this, arg));
     else if (st == "wall/region") {
       int walls = 0;
       for (auto &g : fixes) if (dynamic_cast<FixWallRegion *>(g.get())) walls++;
@@ -1774,7 +1821,10 @@ void Engine::compute_command(std::vector<std::string> &arg) {
 // ComputePropertyLocal::init (src/compute_property_local.cpp:273-280), ComputePairLocal::init (compute_pair_local.cpp:116-126)
 void Engine::init_local_compute(const LocalCompute &c) const {
   if (c.kind == LOCAL_BOND) return;
-  const bool has_pair = pair_lj || pair_zero;
+  const bool has_pair = pair_lj || pair_zero || pair_soft;
+  // (rows of pairs within their cutoff are evaluated with PairLJCut::single on the device; PairSoft::single is not there)
+  if (pair_soft && (c.style == "pair/local" || c.kind == LOCAL_PAIR))
+    throw LammpsError("MI355X engine: compute " + c.style + " rows of interacting pairs are not supported under pair_style soft");
   if (c.style == "property/local") {
     if (!has_pair) throw LammpsError("No pair style is defined for compute property/local");
     return;
@@ -2050,6 +2100,10 @@ void Engine::write_restart(const std::string &path) {
     for (auto &g : group_names) w.str(g);
     w.vec(gmask);
   }
+  if (pair_soft) {             // pair_style soft: the flags above say "no lj/cut, no zero"; A and rc travel in pc_eps / pc_cut
+    w.str("PAIRSOFT");
+    int one = 1; w.pod(one);
+  }
   if (apa) {                   // angles: tables, style and coefficients
     w.str("ANGLES");
     w.pod(nangletypes); w.pod(extra_angle); w.pod(apa); w.pod(nangles);
@@ -2092,6 +2146,7 @@ void Engine::read_restart(const std::string &path) {
       restart_fix_state[id] = b;
     }
     group_names = {"all"}; gmask.clear();
+    pair_soft = false;
     atime = 0.0; atimestep = 0;      // (the reference's restart files do not carry the simulation time either)
     nangletypes = 0; extra_angle = 0; apa = 0; nangles = 0;
     num_angle.clear(); angle_type.clear(); angle_a1.clear(); angle_a2.clear(); angle_a3.clear(); angle_style_name.clear();
@@ -2107,6 +2162,9 @@ void Engine::read_restart(const std::string &path) {
         group_names.resize(ng);
         for (auto &g : group_names) r.str(g);
         r.vec(gmask);
+      } else if (tag == "PAIRSOFT") {
+        int one; r.pod(one);
+        pair_soft = one != 0;
       } else if (tag == "ANGLES") {
         r.pod(nangletypes); r.pod(extra_angle); r.pod(apa); r.pod(nangles);
         r.vec(num_angle); r.vec(angle_type); r.vec(angle_a1); r.vec(angle_a2); r.vec(angle_a3);

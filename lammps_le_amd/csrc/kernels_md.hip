@@ -7,6 +7,7 @@
 // Reference semantics restated here:
 //   FixNVE::initial_integrate / final_integrate   src/fix_nve.cpp:64-104, :108-141
 //   PairLJCut::compute                            src/pair_lj_cut.cpp:68-140
+//   PairSoft::compute                             src/pair_soft.cpp:54-122 (the SOFT variants; arithmetic in soft_inl.h)
 //   BondFENE::compute / BondHarmonic::compute     src/MOLECULE/bond_fene.cpp:52-128, bond_harmonic.cpp:48-101
 //   FixLangevin::post_force_templated<0,...>      src/fix_langevin.cpp:585-778
 //   Neighbor::check_distance                      src/neighbor.cpp:1962-2014
@@ -14,6 +15,7 @@
 //                                                 region_sphere.cpp:152-196, region_block.cpp:213-329, region_cylinder.cpp:287-420
 #include "device.h"
 #include "bin_inl.h"
+#include "soft_inl.h"
 #include <hip/hip_ext.h>
 
 namespace lmp_le {
@@ -277,7 +279,8 @@ __device__ __forceinline__ void fill_bond_table(const BondTable &bt, double *__r
 // one pair term.  The hot loop is written for issue-bound FP64 on CDNA4: branch-free minimum image
 // (v_rndne), reciprocal by v_rcp_f64 + two Newton steps (<= 1 ulp from the reference's IEEE divide),
 // FMA contraction allowed inside this function only (everything else is compiled -ffp-contract=off).
-template <bool EFLAG, bool MINIMG, bool UNIFORM, bool HAS_SB>
+// SOFT: pair_style soft - the same six table columns / u_* scalars hold cutsq, A pi/rc, pi/rc, A (Engine::init_pair_coeffs)
+template <bool EFLAG, bool MINIMG, bool UNIFORM, bool HAS_SB, bool SOFT = false>
 __device__ __forceinline__ void pair_term(const ForceArgs &A, const Box &box, const double *__restrict__ s_tab,
                                           int itype, const double4 &ri, int jraw, const double4 &rj, bool valid,
                                           double &fxi, double &fyi, double &fzi, double (&e)[14]) {
@@ -295,6 +298,26 @@ __device__ __forceinline__ void pair_term(const ForceArgs &A, const Box &box, co
     const int nt2 = A.nt * A.nt, ij = itype * A.nt + (int)rj.w;
     cutsq = s_tab[ij]; lj1 = s_tab[nt2 + ij]; lj2 = s_tab[2 * nt2 + ij];
     if (EFLAG) { lj3 = s_tab[3 * nt2 + ij]; lj4 = s_tab[4 * nt2 + ij]; offs = s_tab[5 * nt2 + ij]; }
+  }
+  if (SOFT) {
+    if (rsq < cutsq && valid) {
+      double evdwl = 0.0;
+      double fpair = soft_pair<EFLAG>(rsq, __builtin_amdgcn_rsq(rsq), lj1, lj2, lj3, evdwl);
+      double factor_lj = 1.0;
+      if (HAS_SB) {
+        int sb = (jraw >> NEIGH_SB_SHIFT) & 3;
+        factor_lj = (sb == 0) ? A.sl0 : (sb == 1) ? A.sl1 : (sb == 2) ? A.sl2 : A.sl3;
+        fpair *= factor_lj;
+      }
+      fxi += delx * fpair; fyi += dely * fpair; fzi += delz * fpair;
+      if (EFLAG) {
+        evdwl *= factor_lj;
+        e[0] += 0.5 * evdwl;
+        e[2] += 0.5 * delx * delx * fpair; e[3] += 0.5 * dely * dely * fpair; e[4] += 0.5 * delz * delz * fpair;
+        e[5] += 0.5 * delx * dely * fpair; e[6] += 0.5 * delx * delz * fpair; e[7] += 0.5 * dely * delz * fpair;
+      }
+    }
+    return;
   }
   if (rsq < cutsq && valid) {
     double r2inv = __builtin_amdgcn_rcp(rsq);
@@ -423,7 +446,7 @@ __device__ __forceinline__ void bond_term(const Box &box, const double *__restri
 // gathers as the pair partners', instead of a chain of dependent loads (table entry -> position, one bond after the
 // other) behind the pair loop.  Stages that hold a bond entry in some lane (the first one; the second for a wavefront
 // with an extruder anchor) run the mixed body, all later ones the plain pair body.
-template <bool EFLAG, bool MINIMG, bool UNIFORM, bool HAS_SB, int LPB, bool AHEAD, bool DIAGP = false, bool ALLSTYLES = false>
+template <bool EFLAG, bool MINIMG, bool UNIFORM, bool HAS_SB, int LPB, bool AHEAD, bool DIAGP = false, bool ALLSTYLES = false, bool SOFT = false>
 __device__ __forceinline__ void pair_loop(const ForceArgs &A, const Box &box, const double *__restrict__ s_tab,
                                           const double *__restrict__ s_bt, int p, int sub, const BeadPre &L, int nall,
                                           int nb, unsigned long long bsh, const double4 &ri, double &fxi, double &fyi,
@@ -431,7 +454,10 @@ __device__ __forceinline__ void pair_loop(const ForceArgs &A, const Box &box, co
   // software pipeline, W neighbors per stage: while the W position gathers of the current stage are in flight the
   // (coalesced) index loads of the next stage are issued, so a stage costs one exposed round trip.  Lists are
   // consumed in groups of W; slots past the end are predicated off (index = own bead, cached).
-  constexpr int W = AHEAD ? 4 : STEP_STAGE_W;
+  // (the soft term holds more live values per slot than lj/cut's: with four slots per stage the throughput shape needs 3 to 5
+  //  registers more than its 128 and the compiler takes them from scratch - 12 to 20 bytes per lane in six of the eight
+  //  instantiations; three slots fit, at 124 to 128 registers, and keep the fourth wave)
+  constexpr int W = AHEAD ? 4 : SOFT ? 3 : STEP_STAGE_W;
   const int itype = (int)ri.w;
   const size_t npad = (size_t)LPB * A.npad;                                             // stride between a lane's entries
   const int *col = A.neigh + p + (size_t)sub * A.npad;
@@ -467,7 +493,7 @@ __device__ __forceinline__ void pair_loop(const ForceArgs &A, const Box &box, co
 #pragma unroll
       for (int u = 0; u < W; u++) {
         if (g0 + u * LPB < nb) { if (bonds_on) bond_term<EFLAG, ALLSTYLES>(box, s_bt, p, ri, c[u], r[u], (unsigned)(bsh >> (BSHIFT_BITS * (g0 + u * LPB))) & 63u, A.bond_minimg != 0, fxi, fyi, fzi, e, flags); }
-        else pair_term<EFLAG, MINIMG, UNIFORM, HAS_SB>(A, box, s_tab, itype, ri, c[u], r[u], k + u < nn, fxi, fyi, fzi, e);
+        else pair_term<EFLAG, MINIMG, UNIFORM, HAS_SB, SOFT>(A, box, s_tab, itype, ri, c[u], r[u], k + u < nn, fxi, fyi, fzi, e);
       }
     } else if (mixed) {
       // rolled over the slots (one copy of each body in the code; unrolled, the two bodies per slot cost ~20 registers)
@@ -478,17 +504,17 @@ __device__ __forceinline__ void pair_loop(const ForceArgs &A, const Box &box, co
 #pragma unroll
         for (int w = 1; w < W; w++) if (u == w) { cu = c[w]; ru = r[w]; }
         if (g0 + u * LPB < nb) { if (bonds_on) bond_term<EFLAG, ALLSTYLES>(box, s_bt, p, ri, cu, ru, (unsigned)(bsh >> (BSHIFT_BITS * (g0 + u * LPB))) & 63u, A.bond_minimg != 0, fxi, fyi, fzi, e, flags); }
-        else pair_term<EFLAG, MINIMG, UNIFORM, HAS_SB>(A, box, s_tab, itype, ri, cu, ru, k + u < nn, fxi, fyi, fzi, e);
+        else pair_term<EFLAG, MINIMG, UNIFORM, HAS_SB, SOFT>(A, box, s_tab, itype, ri, cu, ru, k + u < nn, fxi, fyi, fzi, e);
       }
     } else {
 #pragma unroll
       for (int u = 0; u < W; u++)
-        pair_term<EFLAG, MINIMG, UNIFORM, HAS_SB>(A, box, s_tab, itype, ri, c[u], r[u], k + u < nn, fxi, fyi, fzi, e);
+        pair_term<EFLAG, MINIMG, UNIFORM, HAS_SB, SOFT>(A, box, s_tab, itype, ri, c[u], r[u], k + u < nn, fxi, fyi, fzi, e);
     }
   }
 }
 
-template <bool EFLAG, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ALLSTYLES = false>
+template <bool EFLAG, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ALLSTYLES = false, bool SOFT = false>
 __device__ __forceinline__ void bead_force(const ForceArgs &A, const BondTable &bt, const Box &box,
                                            const double *__restrict__ s_tab, const double *__restrict__ s_bt, int p,
                                            int sub, const BeadPre &L, const double4 &ri, double &fxi, double &fyi,
@@ -505,7 +531,7 @@ __device__ __forceinline__ void bead_force(const ForceArgs &A, const BondTable &
     bool interior = ri.x > box.lo[0] + m && ri.x < box.hi[0] - m && ri.y > box.lo[1] + m && ri.y < box.hi[1] - m &&
                     ri.z > box.lo[2] + m && ri.z < box.hi[2] - m;
     bool all_in = __all(interior);
-#define LE_LOOP(MI, UN, SB) pair_loop<EFLAG, MI, UN, SB, LPB, AHEAD, DIAG, ALLSTYLES>(A, box, s_tab, s_bt, p, sub, L, nall, nb, bsh, ri, fxi, fyi, fzi, e, flags)
+#define LE_LOOP(MI, UN, SB) pair_loop<EFLAG, MI, UN, SB, LPB, AHEAD, DIAG, ALLSTYLES, SOFT>(A, box, s_tab, s_bt, p, sub, L, nall, nb, bsh, ri, fxi, fyi, fzi, e, flags)
     if (A.uniform && !A.has_sb) {
       if (all_in) LE_LOOP(false, true, false); else LE_LOOP(true, true, false);
     } else if (!A.has_sb) {
@@ -701,7 +727,7 @@ __global__ __launch_bounds__(BLOCK) void k_wall(int n, const double4 *__restrict
 
 // forces only (setup, thermo steps, runs without the standard nve+langevin pair of fixes)
 // NOBOND: the bond entries at the head of the lists are skipped (run_style respa with pair and bond forces on different levels)
-template <bool EFLAG, bool HAS_PAIR, bool NOBOND = false>
+template <bool EFLAG, bool HAS_PAIR, bool NOBOND = false, bool SOFT = false>
 __global__ __launch_bounds__(BLOCK) void k_force(ForceArgs A, BondTable bt, Box box, double *__restrict__ fx,
                                                  double *__restrict__ fy, double *__restrict__ fz,
                                                  double *__restrict__ partial, int *__restrict__ flags) {
@@ -720,7 +746,7 @@ __global__ __launch_bounds__(BLOCK) void k_force(ForceArgs A, BondTable bt, Box 
     double4 ri = A.pos[p];
     const BeadPre L = bead_preload<HAS_PAIR, 1, true>(A, p, 0);
     double fxi = 0.0, fyi = 0.0, fzi = 0.0;
-    bead_force<EFLAG, HAS_PAIR, 1, NOBOND, true, true>(A, bt, box, s_tab, s_bt, p, 0, L, ri, fxi, fyi, fzi, e, flags);   // (DIAG = NOBOND: A.diag = 1 switches the bonds off)
+    bead_force<EFLAG, HAS_PAIR, 1, NOBOND, true, true, SOFT>(A, bt, box, s_tab, s_bt, p, 0, L, ri, fxi, fyi, fzi, e, flags);   // (DIAG = NOBOND: A.diag = 1 switches the bonds off)
     fx[p] = fxi; fy[p] = fyi; fz[p] = fzi;
   }
   if (EFLAG && lb < A.nblocks) block_reduce_store<14>(e, partial, lb, 0);
@@ -812,7 +838,7 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // The parameters from `tag` on are the members of S and k_step's five direct pointers once more, __restrict__-qualified: the
 // loads of level 0 / level 1 below and of the AHEAD shapes move ahead of the stores into `flags` only with it (StepKernelArgs).
 // Read straight from S here, the members give 2 instantiations other VGPR counts and the wall variants vector loads of their table.
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL>
+template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL, bool SOFT>
 __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt, const StepKernelArgs &S,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
@@ -858,7 +884,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     d0 = draws[3 * (size_t)rank]; d1 = draws[3 * (size_t)rank + 1]; d2 = draws[3 * (size_t)rank + 2];
   }
   double f0 = 0.0, f1 = 0.0, f2 = 0.0;
-  bead_force<EF, HAS_PAIR, LPB, DIAG, AHEAD>(A, bt, box, s_tab, s_bt, p, sub, L, ri, f0, f1, f2, e, flags);
+  bead_force<EF, HAS_PAIR, LPB, DIAG, AHEAD, false, SOFT>(A, bt, box, s_tab, s_bt, p, sub, L, ri, f0, f1, f2, e, flags);
   if (LPB > 1) {
 #pragma unroll
     for (int o = 1; o < LPB; o <<= 1) { f0 += __shfl_xor(f0, o); f1 += __shfl_xor(f1, o); f2 += __shfl_xor(f2, o); }
@@ -948,7 +974,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   else { vx[p] = a; vy[p] = b; vz[p] = c; }
 }
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
-          bool GRP = false, bool LAZYV = false, bool WALL = false>
+          bool GRP = false, bool LAZYV = false, bool WALL = false, bool SOFT = false>
 __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
                                                                                            StepKernelArgs S, double *__restrict__ fx,
                                                                                            double *__restrict__ fy, double *__restrict__ fz,
@@ -959,6 +985,8 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
                 "the by-value arguments of k_step exceed the 4 KiB kernel-argument limit");
   static_assert(!WALL || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD)),
                 "wall variant: the three plain shapes with a pair style");
+  static_assert(!SOFT || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && (LPB == 1 || AHEAD)),
+                "soft variant: the three plain shapes with a pair style");
   static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
                 "velocity hand-over: the throughput shape only");
   static_assert(!EF || (!NEXT && LPB == 1), "energy variant: NEXT = false, one lane per bead");
@@ -975,7 +1003,7 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL>(
+  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT>(
       A, bt, box, tt, S, s_tab, s_bt, S.tag, S.ranks, S.draws, S.vx, S.vy, S.vz, fx, fy, fz, pos_next, xhold, S.dtv, S.triggersq, S.check, S.flags,
       S.phase, S.which, e, kev[0], S.gmask, S.nvebit, S.lgbit, S.vperm, S.vxo, S.vyo, S.vzo, S.walls);
   if (EF) {
@@ -1156,7 +1184,7 @@ static ForceArgs force_args(DeviceState &d, const double sl[4]) {
   return A;
 }
 // `parts`: 3 = pair + bond (the default), 1 = pair only, 2 = bond only, 0 = nothing (forces zeroed); run_style respa
-void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool eflag, bool has_pair, int parts) {
+void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool eflag, bool has_pair, int parts, bool soft) {
   ForceArgs A = force_args(d, sl);
   int grid = xcd_grid(A.nblocks);
   if (!has_pair) parts &= 2;
@@ -1165,19 +1193,19 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
     return;
   }
   if (parts == 1) A.diag = 1;      // pairs only (bonds only: straight from the bond-partner table)
-  with_flags([&](auto E, auto P, auto NOBOND) {
-    if constexpr (P || !NOBOND)
-      hipLaunchKernelGGL((k_force<E, P, NOBOND>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
-  }, eflag, (parts & 1) != 0, parts == 1);
+  with_flags([&](auto E, auto P, auto NOBOND, auto SOFT) {
+    if constexpr ((P || !NOBOND) && (P || !SOFT))
+      hipLaunchKernelGGL((k_force<E, P, NOBOND, SOFT>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
+  }, eflag, (parts & 1) != 0, parts == 1, soft && (parts & 1) != 0);
 }
-// f(k_step<the plan's eleven template arguments, lazy_v as LAZYV before the last>); false: there is no such instantiation
+// f(k_step<the plan's twelve template arguments, lazy_v as LAZYV before the last two>); false: there is no such instantiation
 template <class F>
 static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
-  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z, auto WL) {
+  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z, auto WL, auto SF) {
     constexpr int W = W4 ? 4 : 1;
-    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL>); found = true; }
-  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v, p.wall);
+    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL, SF)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL, SF>); found = true; }
+  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v, p.wall, p.soft);
   return found;
 }
 // Fills the kernel's argument record from the device state, the plan and the launch's arguments - the one place that does -
@@ -1264,15 +1292,16 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
 // check, cells, walls (StepRequest::walls); out = fused, the plan's first ten template arguments in k_step's order (langevin
 // ... grp), bin, member_ranks, diag_bits, lds_pad, whether the dispatcher of launch_step holds the instantiation the plan names
 // (its own look-up, nothing is launched), then [16] = StepPlan::wall and [17] = the plan takes velocities a rebuild left pending
-static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out) {
+static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out, int soft = 0, int *out_soft = nullptr) {
   StepRequest r;
   r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
-  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls;
+  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0;
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
   const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
   const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
                      p.diag_bits, (int)p.lds_pad, known, p.wall, takes_pending_v(p, decomposed != 0)};
   for (int k = 0; k < 18; k++) out[k] = v[k];
+  if (out_soft) *out_soft = p.soft;
 }
 // eleven inputs (no walls), the first 16 outputs
 extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
@@ -1283,6 +1312,10 @@ extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int 
 // twelve inputs, req[11] = walls; all 18 outputs
 extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, const int *req, int *out) {
   test_step_plan(n_owned, decomposed, req, req[11], out);
+}
+// thirteen inputs, req[11] = walls, req[12] = pair_style soft; the 18 outputs of the hook above, then [18] = StepPlan::soft
+extern "C" void lammps_le_test_step_plan_soft(int n_owned, int decomposed, const int *req, int *out) {
+  test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -73,7 +73,7 @@ def scrambled_chains(nbeads, nchains=1, density=0.85, seed=1, jitter=0.03, temp=
     that is a random Hamiltonian path (backbite moves) inside every block of `block`^3 sites, blocks visited in
     serpentine order (csrc/tools.cpp).  Same density, bond length and barrier typing as lattice_chains; locally the
     walk turns at 77 % of its sites (the serpentine start: 1 %), so a cell's beads carry unrelated tags the way a melt's do.
-    The reference's own generator (tools/chain.f: phantom random walks) needs a soft push-off this engine has no style for."""
+    (phantom_chains is the other kind of start: freely overlapping random walks, to be pushed apart with pair_style soft.)"""
     import ctypes as C
     import os
     rng = np.random.RandomState(seed)
@@ -96,6 +96,53 @@ def scrambled_chains(nbeads, nchains=1, density=0.85, seed=1, jitter=0.03, temp=
     x = (xyz[:n].astype(np.float64) + 0.5) * a
     x += rng.uniform(-jitter, jitter, size=(n, 3))
     return _finish(x, n, nchains, barrier_every, L * a, rng, temp)
+
+
+def phantom_chains(nbeads, nchains=1, density=0.85, seed=1, bond=0.97, restrict=1.02, temp=1.0, barrier_every=0):
+    """Phantom random walks, the kind of start the reference's tools/chain.f writes (restated here in numpy, not a port of it):
+    every chain starts at a uniformly random point of a cubic box of volume nbeads / density centred on the origin and takes
+    steps of length `bond` in directions uniform on the sphere, except that bead i stays farther than `restrict` from bead
+    i - 2.  Beads of different chains, and beads more than two apart along a chain, overlap freely: such a start survives
+    step 0 only under a soft potential (pair_style soft with fix adapt ramping its prefactor), not under lj/cut.
+    Coordinates are wrapped into the box with image flags.  The i-2 rule only limits the angle between consecutive steps
+    (cos > restrict^2 / (2 bond^2) - 1), so step i is drawn in the frame of step i-1 - cos uniform on the allowed cap, azimuth
+    uniform - and the frames are composed by a prefix product of unit quaternions: O(N log N) numpy, no loop over beads."""
+    rng = np.random.RandomState(seed)
+    n, nc = int(nbeads), int(nchains)
+    per = n // nc
+    if per * nc != n or per < 2:
+        raise ValueError("phantom_chains: nbeads must be a multiple of nchains, chains of at least 2 beads")
+    edge = (n / density) ** (1.0 / 3.0)
+    cmin = restrict * restrict / (2.0 * bond * bond) - 1.0
+    if not -1.0 <= cmin < 1.0:
+        raise ValueError("phantom_chains: no step of length %g keeps bead i farther than %g from bead i-2" % (bond, restrict))
+    start = rng.uniform(-0.5 * edge, 0.5 * edge, size=(nc, 3))
+    nb = per - 1
+    cos_t = rng.uniform(cmin, 1.0, size=(nc, nb))
+    cos_t[:, 0] = rng.uniform(-1.0, 1.0, size=nc)              # the first step of a chain: any direction
+    phi = rng.uniform(0.0, 2.0 * np.pi, size=(nc, nb))
+    half_c, half_s = np.sqrt(0.5 * (1.0 + cos_t)), np.sqrt(0.5 * (1.0 - cos_t))
+    # rotation that takes z to (sin t cos p, sin t sin p, cos t): by t about the axis (-sin p, cos p, 0)
+    q = np.stack([half_c, -half_s * np.sin(phi), half_s * np.cos(phi), np.zeros_like(phi)], axis=-1)
+    shift = 1
+    while shift < nb:           # Q_i = q_1 q_2 .. q_i (Hillis-Steele scan over the associative product)
+        a, b = q[:, :-shift], q[:, shift:]
+        aw, ax, ay, az = (a[..., k] for k in range(4))
+        bw, bx, by, bz = (b[..., k] for k in range(4))
+        prod = np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                         aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], axis=-1)
+        q = np.concatenate([q[:, :shift], prod / np.sqrt((prod * prod).sum(axis=-1, keepdims=True))], axis=1)
+        shift *= 2
+    w, qx, qy, qz = (q[..., k] for k in range(4))
+    steps = bond * np.stack([2.0 * (qx * qz + w * qy), 2.0 * (qy * qz - w * qx), 1.0 - 2.0 * (qx * qx + qy * qy)], axis=-1)
+    xu = np.concatenate([start[:, None, :], start[:, None, :] + np.cumsum(steps, axis=1)], axis=1).reshape(n, 3)
+    image = np.floor((xu + 0.5 * edge) / edge).astype(np.int32)
+    x = xu - image * edge
+    x = np.where(x >= 0.5 * edge, -0.5 * edge, x)              # (a coordinate the subtraction rounded onto the upper face)
+    s = _finish(x, n, nc, barrier_every, edge, rng, temp)
+    s["box"] = np.array([[-0.5 * edge, 0.5 * edge]] * 3)
+    s["image"] = image
+    return s
 
 
 def add_backbone_angles(s, nchains=1, atype=1, nangletypes=2, extra_angle=24):
