@@ -157,7 +157,8 @@ void *lammps_extract_fix(void *handle, char *id, int style, int type, int nrow, 
   BEGIN_CAPTURE
     Fix *f = e->find_fix(id);
     if (!f) throw LammpsError(std::string("Could not find fix ID ") + id);
-    const bool scalar = style == 0 && type == 0 && dynamic_cast<FixWallRegion *>(f);      // (the one fix with a global scalar)
+    // (the fixes with a global scalar: wall/region, spring/self, addforce)
+    const bool scalar = style == 0 && type == 0 && (dynamic_cast<FixWallRegion *>(f) || dynamic_cast<FixSpringSelf *>(f) || dynamic_cast<FixAddForce *>(f));
     if (!scalar && (style != 0 || type != 1)) throw LammpsError("MI355X engine: only global fix vectors can be extracted");
     if (!scalar && f->size_vector() >= 0 && (nrow < 0 || nrow >= f->size_vector()))
       throw LammpsError("MI355X engine: fix vector is accessed out-of-range");
@@ -650,7 +651,7 @@ static const std::vector<std::pair<std::string, std::vector<std::string>>> &styl
       {"bond", {"fene", "harmonic", "hybrid", "none", "zero"}},
       {"compute", {"pair/local", "property/local"}},
       {"dump", {"atom", "custom", "dcd", "local"}},
-      {"fix", {"adapt", "bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve", "wall/region"}},
+      {"fix", {"adapt", "addforce", "bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve", "setforce", "spring/self", "wall/region"}},
       {"pair", {"lj/cut", "none", "soft", "zero"}},
   };
   return t;
@@ -826,6 +827,7 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "steps_fused_group") return (double)e->steps_fused_group;
   if (k == "steps_fused_thermo") return (double)e->steps_fused_thermo;
   if (k == "steps_unfused") return (double)e->steps_unfused;
+  if (k == "steps_fused_ext") return (double)e->steps_fused_ext;        // of steps_fused: spring/self, addforce, setforce inside the step kernel
   if (k == "steps_fused_wall") return (double)e->steps_fused_wall;      // of steps_fused: fix wall/region inside the step kernel
   if (k == "steps_fused_soft") return (double)e->steps_fused_soft;      // of steps_fused: pair_style soft inside the step kernel
   if (k == "pair_table_copies") return (double)e->pair_table_copies;    // fix adapt: copies of the pair table in the middle of runs

@@ -307,6 +307,14 @@ struct DeviceState {
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
   WallTable *walltab_dev = nullptr;                     // fix wall/region: this run's table (k_wall, the wall variant of k_step)
   double *wall_partial = nullptr;                       // [WALL_MAX][nred_blocks + 1][16] block sums of k_wall<EFLAG> + their totals
+  // fix spring/self | addforce | setforce: this run's table (k_fixforce, the EXT variant of k_step); one block of unwrapped
+  // origins per spring/self fix, [3][ntotal + 1] by tag, never permuted, whole on every rank of a decomposed run
+  ForceOpTable *forceoptab_dev = nullptr;
+  double *forceop_origin[FORCEOP_MAX] = {nullptr};
+  bool forceop_grouped = false;                         // an entry of the table acts on a group other than all
+  ForceOpTable forceoptab_last{};                       // the table those sums belong to (origin addresses nulled) and the bead count:
+  int forceop_rows_n = -1;                              //   the rows are kept over a `run` command while both stay the same
+  double *forceop_partial = nullptr;                    // [FORCEOP_MAX][nred_blocks + 1][16] block sums of k_fixforce<EFLAG> + their totals
   AngleTable *angtab_dev = nullptr;                     // this run's table in device memory (fused angle step)
   bool ghost_whole_shell = false;                       // every bead within the ghost cutoff of a face is sent (runs with an angle style)
   bool map_stale = true;                                // map[] was not left by a decomposed rebuild: fill it before the next one
@@ -400,6 +408,7 @@ struct StepArgs {
   double dtv = 0.0, triggersq = 0.0;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // sampled launches: the kernel's own begin / end timestamps
   bool swap_buffers = true;                           // a `next` launch leaves the new positions in d.pos
+  unsigned ext_active = 0;                            // EXT: bit k - entry k of the force-op table acts on this step (addforce `every`)
 };
 void launch_step(DeviceState &d, const StepPlan &plan, const StepArgs &args);
 void launch_langevin(DeviceState &d, const TypeTables &tt, bool identity_rank, bool fuse_final, int groupbit = 1);
@@ -421,6 +430,13 @@ void reduce_angle_partials(DeviceState &d, double *out8);
 void upload_wall_table(DeviceState &d, const WallTable &wt);
 void launch_wall(DeviceState &d, const WallTable &wt, int phase, bool eflag);
 void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out);
+// fix spring/self | addforce | setforce (kernels_md.hip): the table of a run with the origin blocks (`origins[k]`: the host
+// block [natoms][3] of entry k, null for an entry that has none; the table's entries get the device addresses); the entries of
+// one phase applied to f in table order (`active`: bit k - entry k acts on this step; eflag: with the ten block sums per
+// entry); those sums on the host, rows of 16 per entry (synchronises the stream)
+void upload_forceop_table(DeviceState &d, ForceOpTable &ft, const double *const *origins, int natoms);
+void launch_fixforce(DeviceState &d, const ForceOpTable &ft, int phase, unsigned active, bool eflag);
+void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *out);
 // reductions: returns sums of `partial` columns on the host (synchronises the stream)
 void reduce_partials(DeviceState &d, double *out16);
 

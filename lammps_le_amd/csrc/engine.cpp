@@ -928,6 +928,58 @@ void Engine::build_wall_table() {
 }
 void Engine::wall_post_force(int phase, bool eflag) {
   if (walltab.n) launch_wall(*dev, walltab, phase, eflag);
+  forceop_post_force(phase, eflag);      // within a phase the walls act first (build_forceop_table holds the scripts to that)
+}
+
+// fix spring/self | addforce | setforce: the table of this run, in fix order (the order the reference runs post_force in, which
+// setforce's overwrite and the foriginal sums of addforce / setforce see).  The kernels run the walls of a phase ahead of these
+// entries, so an addforce or setforce defined ahead of a wall on the same side of fix langevin would see the wrong force: refused.
+// spring/self adds a force that depends on the position alone and may stand anywhere.
+void Engine::build_forceop_table() {
+  forceoptab = ForceOpTable{};
+  forceop_fixes.clear();
+  forceoptab.stride = natoms + 1;
+  int phase = 0;
+  bool order_matters[2] = {false, false};     // an addforce / setforce was seen in this phase
+  for (auto &f : fixes) {
+    if (dynamic_cast<FixLangevin *>(f.get())) phase = 1;
+    if (dynamic_cast<FixWallRegion *>(f.get()) && order_matters[phase])
+      throw LammpsError("MI355X engine: fix " + f->id + " (wall/region) is defined behind a fix addforce or setforce on the same side of "
+                        "fix langevin; define the wall first");
+    auto *o = dynamic_cast<FixForceOp *>(f.get());
+    if (!o) continue;
+    if (forceoptab.n >= FORCEOP_MAX) throw LammpsError("internal: more than FORCEOP_MAX force fixes");
+    ForceOpEntry e = o->entry();
+    e.phase = phase;
+    if (o->kind != FORCEOP_SPRING) order_matters[phase] = true;
+    forceoptab.e[forceoptab.n++] = e;
+    forceop_fixes.push_back(o);
+  }
+}
+unsigned Engine::forceop_active() const {
+  unsigned m = 0;
+  for (int k = 0; k < forceoptab.n; k++) if (ntimestep % forceoptab.e[k].every == 0) m |= 1u << k;
+  return m;
+}
+// An addforce with `every N` reports, on a thermo step it skips, the sums of the last step on which it acted: that step takes the
+// unfused kernels with the block sums, like a thermo step.  True when `ntimestep` is such a step: an entry with N > 1 acts now and
+// the next thermo step (a multiple of `thermo`, or the end of the run) comes before it acts again
+static bool forceop_sums_due(const Engine *e) {
+  for (int k = 0; k < e->forceoptab.n; k++) {
+    const long every = e->forceoptab.e[k].every;
+    if (every <= 1 || e->ntimestep % every) continue;
+    long next = e->endstep;
+    if (e->thermo_every > 0) next = std::min(next, (e->ntimestep / e->thermo_every + 1) * (long)e->thermo_every);
+    if (next > e->ntimestep && next - e->ntimestep < every) return true;
+  }
+  return false;
+}
+void Engine::forceop_post_force(int phase, bool eflag) {
+  if (forceoptab.n) launch_fixforce(*dev, forceoptab, phase, forceop_active(), eflag);
+}
+static bool forceops_behind_langevin(const Engine *e) {
+  for (int k = 0; k < e->forceoptab.n; k++) if (e->forceoptab.e[k].phase) return true;
+  return false;
 }
 static int walls_request(const Engine *e) {      // StepRequest::walls
   if (!e->walltab.n) return 0;
@@ -998,11 +1050,13 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
   TypeTables tt = make_tables(this, nullptr);
   if (!ke_summed) launch_ke(d, tt);       // (the energy variant of the step kernel has summed the kinetic energy as well)
   // behind the sixteen sums of the force kernel: the ten of every wall (rows of 16), in the same all-reduce
-  double s[16 + 16 * WALL_MAX];
+  // ... and behind those the ten of every spring/self, addforce and setforce
+  double s[16 + 16 * WALL_MAX + 16 * FORCEOP_MAX];
   reduce_partials(d, s);
-  const int nwall = walltab.n;
+  const int nwall = walltab.n, nops = forceoptab.n;
   if (nwall) reduce_wall_partials(d, walltab, s + 16);
-  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * nwall);
+  if (nops) reduce_fixforce_partials(d, forceoptab, s + 16 + 16 * nwall);
+  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * (nwall + nops));
   double efix = 0.0, vfix[6] = {0, 0, 0, 0, 0, 0};      // Modify::thermo_energy (src/compute_pe.cpp:102), the fixes of compute_pressure.cpp:201-220
   for (int k = 0; k < nwall; k++) {
     FixWallRegion *w = wall_fixes[k];
@@ -1011,6 +1065,17 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
     for (int c = 0; c < 6; c++) w->virial[c] = ws[4 + c];
     if (w->thermo_energy) efix += w->ewall[0];
     if (w->thermo_virial) for (int c = 0; c < 6; c++) vfix[c] += w->virial[c];
+  }
+  for (int k = 0; k < nops; k++) {
+    FixForceOp *o = forceop_fixes[k];
+    // (an addforce that skipped this step - `every` - returned before it touched its sums, src/fix_addforce.cpp:243: the rows
+    //  of block sums are then those of the last step on which it acted, which forceop_sums_due had evaluated with them)
+    //  The six virial terms are different: v_tally runs only on a step that wants the virial, so after a skipped thermo step
+    //  the reference's array still holds what the last thermo step on which the fix acted left (:247-248, :292-300)
+    const bool acted = (forceop_active() >> k) & 1u;
+    for (int c = 0; c < FORCEOP_COLS; c++) if (c < 4 || acted) o->sums[c] = s[16 + 16 * (nwall + k) + c];
+    if (o->thermo_energy) efix += o->compute_scalar();
+    if (o->thermo_virial) for (int c = 0; c < 6; c++) vfix[c] += o->sums[4 + c];
   }
   ThermoRow r{};
   r.step = ntimestep;
@@ -1170,7 +1235,7 @@ void Engine::setup() {
   double s1 = wall();
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = 0;
   adapt_apply(true);                              // FixAdapt::setup_pre_force
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
@@ -1216,6 +1281,7 @@ void Engine::iterate(long nsteps) {
   rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_force(); rq.soft = pair_soft; rq.angles = ang;
   rq.nvebit = fusable ? nbits[0] : 1; rq.lgbit = lg ? lg->groupbit : 1;
   rq.walls = walls_request(this);
+  rq.ext = forceoptab.n > 0;
   bool pre_integrated = false;
   const bool adapting = have_adapt();
   // halo/compute overlap issues the per-step halo on a second stream.  With RCCL that means two streams feeding ONE
@@ -1237,13 +1303,15 @@ void Engine::iterate(long nsteps) {
     bool eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0);
     const bool restart_now = restart_every > 0 && ntimestep % restart_every == 0;
     const bool dump_now = (!dumps.empty() && dump_due(ntimestep)) || restart_now;   // needs the complete state of this step: unfused path
+    const bool ext_sums = !eflag && forceop_sums_due(this);      // (the fixes' block sums of this step are wanted: unfused, no thermo row)
     TypeTables tt = make_tables(this, lg);
     // the plan of this step: a dump / restart needs the complete state of the step, which the unfused kernels leave
-    rq.next = it + 1 < nsteps; rq.thermo = eflag; rq.which = -1; rq.check = false;
+    rq.next = it + 1 < nsteps; rq.thermo = eflag || ext_sums; rq.which = -1; rq.check = false;
     auto plan_now = [&]() { return fusable && !dump_now ? plan_step(d.n, d.dd != 0, rq, step_knobs) : StepPlan(); };
     StepPlan plan = plan_now();
     StepArgs sa;
     sa.bt = &bondtab; sa.special_lj = special_lj; sa.tt = &tt; sa.dtv = dt; sa.triggersq = triggersq;
+    sa.ext_active = forceop_active();      // (of the step whose forces the launch computes: this one, not its NEXT half's)
     stamp();
     if (!pre_integrated) {
       bool will_check = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
@@ -1315,6 +1383,7 @@ void Engine::iterate(long nsteps) {
       if (plan.grp) steps_fused_group++;
       if (plan.wall) steps_fused_wall++;
       if (plan.soft) steps_fused_soft++;
+      if (plan.ext) steps_fused_ext++;
       stamp(T_PAIR);          // the fused kernel: pair + bond + post_force + final_integrate (+ next initial_integrate)
     } else if (plan.fused) {
       // a thermo step without dumps: the step kernel's energy variant - forces, energies, virial, post_force and
@@ -1339,11 +1408,11 @@ void Engine::iterate(long nsteps) {
       stamp(T_PAIR);          // k_force: pair + bond in one pass
       // (Langevin and the final half-kick in one kernel only when both fixes act on the same atoms)
       // fix wall/region at its place among the post-force fixes: before fix langevin, or behind it (no fused half-kick then)
-      wall_post_force(0, eflag);
+      wall_post_force(0, eflag || ext_sums);
       const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag &&
-                                  !walls_behind_langevin(this);
+                                  !walls_behind_langevin(this) && !forceops_behind_langevin(this);
       if (lg) langevin_post_force(this, lg, lg_fused_final);
-      wall_post_force(1, eflag);
+      wall_post_force(1, eflag || ext_sums);
       if (!lg_fused_final)
         for (int k = 0; k < nnve; k++) launch_final_integrate(d, tt, nbits[k]);
       pre_integrated = false;
@@ -1390,7 +1459,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = 0;
   for (int l = 0; l <= top; l++) {
     if (l == top) adapt_apply(true);           // FixAdapt::setup_pre_force_respa: the outermost level only
     respa_level_forces(l);
@@ -1398,7 +1467,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   }
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
-  if (lg || walltab.n) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
+  if (lg || walltab.n || forceoptab.n) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
     launch_flevel_copy(d, d.respa_flevel[top], false, false);     // FixWallRegion::setup likewise (ilevel_respa = the outermost)
     wall_post_force(0, true);
     if (lg) langevin_post_force(this, lg, false);
@@ -1456,7 +1525,7 @@ void Engine::respa_recurse(int l, bool last) {
     stamp(T_PAIR);
     // post_force_respa at the outermost level (src/fix_langevin.cpp:576-579, src/fix_wall_region.cpp:306-309), in fix order; a
     // thermo step also takes the walls' sums (the positions are the step's last)
-    const bool wall_eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0);
+    const bool wall_eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0) || forceop_sums_due(this);
     if (l == top) wall_post_force(0, wall_eflag);
     if (l == top && lg) langevin_post_force(this, lg, false);
     if (l == top) wall_post_force(1, wall_eflag);
@@ -1537,6 +1606,7 @@ void Engine::run(long nsteps) {
   const bool trace = getenv("LAMMPS_LE_TRACE_RUN") != nullptr;
   double tr0 = wall();
   init();
+  build_forceop_table();      // (beside build_wall_table below, but ahead of the upload: what it refuses needs no device)
   rebuild_knobs = RebuildKnobs();
   double tr1 = wall();
   // (the fixes on groups are not those of the last upload: the masks, the member ranks and the thermostat's member count travel
@@ -1554,6 +1624,12 @@ void Engine::run(long nsteps) {
   // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
   //  region ends every rank - the error flag travels with the displacement test's reduction, Engine::decide)
   if (walltab.n) upload_wall_table(*dev, walltab);
+  // fix spring/self | addforce | setforce: the table (built above) and the origin blocks of the tethers (by tag, whole on every rank)
+  if (forceoptab.n) {
+    std::vector<const double *> origins;
+    for (auto *o : forceop_fixes) origins.push_back(o->kind == FORCEOP_SPRING ? o->xorig.data() : nullptr);
+    upload_forceop_table(*dev, forceoptab, origins.data(), natoms);
+  }
   if (dev->dd) dd_fast_halo_switch(*dev);
   for (int k = 1; k <= 3; k++) dev->sflag[k] = special_flag(k);
   set_xhold_alias(*dev, !dev->dd && !rebuild_knobs.no_xhold_alias);

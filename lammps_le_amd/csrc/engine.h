@@ -39,6 +39,7 @@ constexpr int NN_NBOND_MASK = 0xFF;          // bond entries of the word: (word 
 // two bits per dimension and bond slot in DeviceState::bshift (0 none, 1 partner at +prd, 2 partner at -prd)
 constexpr int NN_SHIFTED_BIT = 1 << 30;
 constexpr int BSHIFT_BITS = 6;
+constexpr int FORCEOP_MAX = 8;    // fix spring/self | addforce | setforce instances one run can hold (ForceOpTable)
 constexpr int WALL_MAX = 4;        // fix wall/region instances one run can hold (WallTable)
 
 // ---------------------------------------------------------------------------------------------
@@ -104,6 +105,27 @@ struct WallTable {
   int n;
   WallEntry w[WALL_MAX];
 };
+
+// fix spring/self | addforce | setforce (src/fix_spring_self.cpp, fix_addforce.cpp, fix_setforce.cpp): the post-force fixes that
+// act on chosen beads from outside, in the order the fixes were defined; built on the host at every `run`
+enum ForceOpKind { FORCEOP_SPRING = 0, FORCEOP_ADD = 1, FORCEOP_SET = 2 };
+struct ForceOpEntry {
+  int kind;                   // ForceOpKind
+  int groupbit;               // the fix's group (1 = all)
+  int phase;                  // 0: before fix langevin or without one, 1: behind it
+  int every;                  // addforce `every N`: acts on steps with ntimestep % N == 0 (the host states it per launch)
+  int mask;                   // bit c: spring/self has a spring along c | setforce sets component c (addforce: 7)
+  int pad;
+  double k;                   // spring/self: the spring constant
+  double v[3];                // addforce | setforce: the three values
+  const double *origin;       // spring/self: [3][stride] unwrapped origins by tag, device memory (members only are read)
+};
+struct ForceOpTable {
+  int n;
+  int stride;                 // natoms + 1: the row length of every origin block
+  ForceOpEntry e[FORCEOP_MAX];
+};
+constexpr int FORCEOP_COLS = 10;   // sums per entry: energy, foriginal x y z, virial xx yy zz xy xz yz
 
 struct DeviceState;  // defined in device.h (HIP side)
 struct Comm;         // defined in comm.h
@@ -216,6 +238,28 @@ struct FixWallRegion : Fix {
   int size_vector() const override { return 3; }
   bool extensive() const override { return true; }       // (src/fix_wall_region.cpp:45-46)
 };
+
+// fix ID group spring/self K [dir] | addforce fx fy fz [every N] | setforce fx|NULL fy|NULL fz|NULL.  The force lives in
+// kernels_md.hip (forceops_on_bead); the objects hold the script's numbers, the origins and the sums of the last evaluation
+struct FixForceOp : Fix {
+  int kind = FORCEOP_SPRING;
+  int every = 1, mask = 7;
+  double k = 0.0, v[3] = {0, 0, 0};
+  bool has_energy = false, has_virial = false;           // what fix_modify energy / virial may switch on for this style
+  bool thermo_energy = false, thermo_virial = false;
+  std::string estr;                                      // addforce `energy v_name`: refused at run, as the reference's init()
+  std::vector<double> xorig;                             // spring/self: [natoms][3] unwrapped origins by tag - 1 (non-members 0)
+  double sums[FORCEOP_COLS] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // of the last thermo evaluation on which the fix acted
+  void init() override;
+  ForceOpEntry entry() const;
+  int size_vector() const override { return kind == FORCEOP_SPRING ? 0 : 3; }
+  bool extensive() const override { return true; }       // extscalar / extvector = 1 in all three
+  double compute_scalar() override;
+  double compute_vector(int n) override;
+};
+struct FixSpringSelf : FixForceOp { FixSpringSelf(Engine *e, const std::vector<std::string> &arg); };
+struct FixAddForce : FixForceOp { FixAddForce(Engine *e, const std::vector<std::string> &arg); };
+struct FixSetForce : FixForceOp { FixSetForce(Engine *e, const std::vector<std::string> &arg); };
 
 // fix ID group adapt N pair soft a | lj/cut epsilon | lj/cut sigma I J v_name [pair ...] [reset yes|no] [scale yes|no]
 // (src/fix_adapt.cpp).  Holds the script's words; the values are set by Engine::adapt_apply at setup of every run and before the
@@ -388,6 +432,13 @@ class Engine {
   std::vector<FixWallRegion *> wall_fixes;
   void build_wall_table();            // at every run (init() has checked the regions); emptied when the set of fixes changes
   void wall_post_force(int phase, bool eflag);   // k_wall for the walls before (0) / behind (1) fix langevin
+  // fix spring/self | addforce | setforce: the table of this run (fix order), the fixes behind its rows
+  ForceOpTable forceoptab{};
+  std::vector<FixForceOp *> forceop_fixes;
+  long steps_fused_ext = 0;           // of steps_fused: the step kernel's EXT variant (these fixes inside the kernel)
+  void build_forceop_table();         // at every run, beside build_wall_table(); checks the order against the walls
+  unsigned forceop_active() const;    // bit k: entry k acts on step ntimestep (addforce `every`)
+  void forceop_post_force(int phase, bool eflag);   // k_fixforce for the entries of one phase, behind that phase's walls
   StepKnobs step_knobs;        // the step kernel's environment switches as they stood when the current run began
   RebuildKnobs rebuild_knobs;  // ... and the rebuild's
   unsigned rebuild_plan_bits = 0;   // the plan the last rebuild (or regrow pass) executed, lammps_le_stat("rebuild_plan_full")
@@ -494,6 +545,7 @@ class Engine {
   int restart_toggle = 0;
   void write_periodic_restart(long step);
   std::map<std::string, std::vector<unsigned char>> restart_fix_state;   // fix ID -> saved state, applied by `fix`
+  std::map<std::string, std::vector<double>> restart_origins;            // fix ID -> origins of a fix spring/self in the file
   void apply_restart_state(Fix *f);
   bool dump_due(long step) const;
   void write_dumps(long step);       // downloads, then writes every dump that is due

@@ -72,6 +72,125 @@ FixLangevin::FixLangevin(Engine *e, const std::vector<std::string> &arg) {
   has_post_force = true;
 }
 
+// fix ID group spring/self K [xyz|xy|xz|yz|x|y|z]  (src/fix_spring_self.cpp:34-91).  The origin of a member is its unwrapped
+// position at this command (Domain::unmap: x + image * prd); when a run has left the newest state on the device it is fetched
+// first - a whole-system download, the command is not on the hot path
+FixSpringSelf::FixSpringSelf(Engine *e, const std::vector<std::string> &arg) {
+  eng = e; id = arg[0]; group = arg[1]; style = arg[2];
+  kind = FORCEOP_SPRING;
+  const char *ill = "Illegal fix spring/self command";
+  if (arg.size() < 4 || arg.size() > 5) throw LammpsError(ill);
+  groupbit = fix_group(e, arg);
+  k = numeric(arg[3]);
+  if (k <= 0.0) throw LammpsError(ill);
+  if (arg.size() == 5) {
+    const std::string &w = arg[4];
+    if (w == "xyz") mask = 7;
+    else if (w == "xy") mask = 3;
+    else if (w == "xz") mask = 5;
+    else if (w == "yz") mask = 6;
+    else if (w == "x") mask = 1;
+    else if (w == "y") mask = 2;
+    else if (w == "z") mask = 4;
+    else throw LammpsError(ill);
+  }
+  e->download();
+  const int n = e->natoms;
+  xorig.assign(3 * (size_t)n, 0.0);
+  for (int i = 0; i < n; i++) {
+    if (groupbit != 1 && !(e->gmask[i] & groupbit)) continue;
+    for (int c = 0; c < 3; c++) xorig[3 * (size_t)i + c] = e->x[3 * (size_t)i + c] + e->image[3 * (size_t)i + c] * e->box.prd[c];
+  }
+  has_energy = true;                 // THERMO_ENERGY in setmask(); no virial_flag
+  has_post_force = true;
+}
+
+// one force word of addforce / setforce: a number, `v_name` (refused: the values would have to be evaluated per step, or per
+// bead, between two launches), or - setforce - NULL
+static bool force_word(const std::string &w, const std::string &style, bool null_ok, double &val) {
+  if (w.rfind("v_", 0) == 0)
+    throw LammpsError("MI355X engine: fix " + style + " with a variable force (" + w + ") is not supported, equal- or atom-style");
+  if (null_ok && w == "NULL") return false;
+  val = numeric(w);
+  return true;
+}
+
+// fix ID group addforce fx fy fz [every N] [region R] [energy v_name]  (src/fix_addforce.cpp:36-119)
+FixAddForce::FixAddForce(Engine *e, const std::vector<std::string> &arg) {
+  eng = e; id = arg[0]; group = arg[1]; style = arg[2];
+  kind = FORCEOP_ADD;
+  const char *ill = "Illegal fix addforce command";
+  if (arg.size() < 6) throw LammpsError(ill);
+  groupbit = fix_group(e, arg);
+  for (int c = 0; c < 3; c++) force_word(arg[3 + c], style, false, v[c]);
+  for (size_t a = 6; a < arg.size(); a += 2) {
+    if (arg[a] == "every") {
+      if (a + 2 > arg.size()) throw LammpsError(ill);
+      every = atoi(arg[a + 1].c_str());
+      if (every <= 0) throw LammpsError(ill);
+    } else if (arg[a] == "region") {
+      if (a + 2 > arg.size()) throw LammpsError(ill);
+      if (!e->regions.count(arg[a + 1])) throw LammpsError("Region ID for fix addforce does not exist");
+      throw LammpsError("MI355X engine: fix addforce with the region keyword is not supported");
+    } else if (arg[a] == "energy") {
+      if (a + 2 > arg.size()) throw LammpsError(ill);
+      if (arg[a + 1].rfind("v_", 0) != 0) throw LammpsError(ill);
+      estr = arg[a + 1].substr(2);
+    } else throw LammpsError(ill);
+  }
+  has_energy = has_virial = true;    // THERMO_ENERGY, virial_flag = 1
+  has_post_force = true;
+}
+
+// fix ID group setforce fx|NULL fy|NULL fz|NULL [region R]  (src/fix_setforce.cpp:36-106)
+FixSetForce::FixSetForce(Engine *e, const std::vector<std::string> &arg) {
+  eng = e; id = arg[0]; group = arg[1]; style = arg[2];
+  kind = FORCEOP_SET;
+  const char *ill = "Illegal fix setforce command";
+  if (arg.size() < 6) throw LammpsError(ill);
+  groupbit = fix_group(e, arg);
+  mask = 0;
+  for (int c = 0; c < 3; c++) if (force_word(arg[3 + c], style, true, v[c])) mask |= 1 << c;
+  for (size_t a = 6; a < arg.size(); a += 2) {
+    if (arg[a] == "region") {
+      if (a + 2 > arg.size()) throw LammpsError(ill);
+      if (!e->regions.count(arg[a + 1])) throw LammpsError("Region ID for fix setforce does not exist");
+      throw LammpsError("MI355X engine: fix setforce with the region keyword is not supported");
+    } else throw LammpsError(ill);
+  }
+  has_post_force = true;
+}
+
+// init() of the three (src/fix_addforce.cpp:149-210, fix_setforce.cpp:134-197)
+void FixForceOp::init() {
+  if (kind == FORCEOP_ADD && !estr.empty()) {
+    if (!eng->variables.count(estr)) throw LammpsError("Variable name for fix addforce does not exist");
+    throw LammpsError("Cannot use variable energy with constant force in fix addforce");
+  }
+  // setforce under r-RESPA zeroes the members' force on every level but one: not carried by the per-level arrays here
+  if (kind == FORCEOP_SET && eng->respa_levels > 0)
+    throw LammpsError("MI355X engine: fix setforce under run_style respa is not supported (it acts on every level)");
+  if (kind == FORCEOP_SPRING && xorig.size() != 3 * (size_t)eng->natoms)
+    throw LammpsError("MI355X engine: the atom count changed since fix spring/self " + id + " stored its origins");
+}
+ForceOpEntry FixForceOp::entry() const {
+  ForceOpEntry o{};
+  o.kind = kind; o.groupbit = groupbit; o.every = every; o.mask = mask; o.k = k;
+  for (int c = 0; c < 3; c++) o.v[c] = v[c];
+  return o;
+}
+// spring/self: the spring energy (fix_spring_self.cpp:176-179: the sum of k * d^2, halved); addforce: -sum f . x_unwrapped
+double FixForceOp::compute_scalar() {
+  if (kind == FORCEOP_SPRING) return 0.5 * sums[0];
+  if (kind == FORCEOP_ADD) return sums[0];
+  throw LammpsError("Fix does not compute a scalar");
+}
+// addforce | setforce: the members' total force before the fix acted (foriginal)
+double FixForceOp::compute_vector(int n) {
+  if (kind == FORCEOP_SPRING) throw LammpsError("Fix does not compute a vector");
+  return sums[1 + n];
+}
+
 // fix ID group adapt N pair pstyle pparam I J v_name ... [reset yes|no] [scale yes|no]  (src/fix_adapt.cpp:45-215).  Pair
 // parameters only, and of those the ones PairSoft::extract and PairLJCut::extract expose: soft a, lj/cut epsilon, lj/cut sigma.
 // The group is parsed and, as in the reference, not used for pair parameters.

@@ -584,31 +584,51 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
       if (walls >= WALL_MAX)
         throw LammpsError("MI355X engine: at most " + std::to_string(WALL_MAX) + " fix wall/region instances (WALL_MAX in engine.h)");
     }
+    else if (st == "spring/self" || st == "addforce" || st == "setforce") {
+      int ops = 0;
+      for (auto &g : fixes) if (dynamic_cast<FixForceOp *>(g.get())) ops++;
+      if (st == "spring/self") f.reset(new FixSpringSelf(this, arg));
+      else if (st == "addforce") f.reset(new FixAddForce(this, arg));
+      else f.reset(new FixSetForce(this, arg));
+      if (ops >= FORCEOP_MAX)
+        throw LammpsError("MI355X engine: at most " + std::to_string(FORCEOP_MAX) +
+                          " fix spring/self, addforce and setforce instances (FORCEOP_MAX in engine.h)");
+    }
     else throw LammpsError("Unknown fix style " + st);
     apply_restart_state(f.get());     // a fix re-specified after read_restart continues its RNG stream (Fix::restart)
     fixes.push_back(std::move(f));
     walltab.n = 0; wall_fixes.clear();      // (the next run builds the table of its walls)
+    forceoptab.n = 0; forceop_fixes.clear();
   } else if (cmd == "unfix") {
     need(1);
     auto it = std::find_if(fixes.begin(), fixes.end(), [&](const std::unique_ptr<Fix> &f) { return f->id == arg[0]; });
     if (it == fixes.end()) throw LammpsError("Could not find fix ID to delete");
     fixes.erase(it);
     walltab.n = 0; wall_fixes.clear();
+    forceoptab.n = 0; forceop_fixes.clear();
   } else if (cmd == "fix_modify") {
     // src/modify.cpp:1052-1066 modify_fix, src/fix.cpp:134-176 modify_params: energy / virial for a fix that has them
     if (arg.size() < 2) throw LammpsError("Illegal fix_modify command");
     Fix *f = find_fix(arg[0]);
     if (!f) throw LammpsError("Could not find fix_modify ID");
     auto *w = dynamic_cast<FixWallRegion *>(f);
+    auto *o = dynamic_cast<FixForceOp *>(f);
     for (size_t k = 1; k < arg.size(); k += 2) {
       if (k + 2 > arg.size()) throw LammpsError("Illegal fix_modify command");
       const std::string &kw = arg[k], &val = arg[k + 1];
       if (kw == "energy" || kw == "virial") {
         if (val != "yes" && val != "no") throw LammpsError("Illegal fix_modify command");
-        if (!w) throw LammpsError("Illegal fix_modify command");      // (no other fix here has THERMO_ENERGY / virial_flag)
-        (kw == "energy" ? w->thermo_energy : w->thermo_virial) = val == "yes";
+        // (spring/self and addforce have THERMO_ENERGY, addforce alone a virial_flag: `no` is always legal, `yes` only with the
+        //  capability, src/fix.cpp:146-163)
+        if (o && (val == "no" || (kw == "energy" ? o->has_energy : o->has_virial))) (kw == "energy" ? o->thermo_energy : o->thermo_virial) = val == "yes";
+        else if (o) throw LammpsError("Illegal fix_modify command");
+        else if (!w) throw LammpsError("Illegal fix_modify command");      // (no other fix here has THERMO_ENERGY / virial_flag)
+        else (kw == "energy" ? w->thermo_energy : w->thermo_virial) = val == "yes";
       } else if (kw == "respa" && w) {
         throw LammpsError("MI355X engine: fix_modify respa is not supported (fix wall/region acts at the outermost level)");
+      } else if (kw == "respa" && o) {
+        throw LammpsError("MI355X engine: fix_modify respa is not supported (fix " + o->style +
+                          (o->kind == FORCEOP_SET ? " is refused under run_style respa)" : " acts at the outermost level)"));
       } else throw LammpsError("Illegal fix_modify command");
     }
   } else if (cmd == "thermo") {
@@ -2104,6 +2124,16 @@ void Engine::write_restart(const std::string &path) {
     w.str("PAIRSOFT");
     int one = 1; w.pod(one);
   }
+  {                            // fix spring/self: the origins, keyed by fix ID (the reference's restart_peratom)
+    uint64_t ns = 0;
+    for (auto &f : fixes) if (dynamic_cast<FixSpringSelf *>(f.get())) ns++;
+    if (ns) {
+      w.str("SPRINGSELF");
+      w.pod(ns);
+      for (auto &f : fixes)
+        if (auto *sp = dynamic_cast<FixSpringSelf *>(f.get())) { w.str(sp->id); w.vec(sp->xorig); }
+    }
+  }
   if (apa) {                   // angles: tables, style and coefficients
     w.str("ANGLES");
     w.pod(nangletypes); w.pod(extra_angle); w.pod(apa); w.pod(nangles);
@@ -2147,6 +2177,7 @@ void Engine::read_restart(const std::string &path) {
     }
     group_names = {"all"}; gmask.clear();
     pair_soft = false;
+    restart_origins.clear();
     atime = 0.0; atimestep = 0;      // (the reference's restart files do not carry the simulation time either)
     nangletypes = 0; extra_angle = 0; apa = 0; nangles = 0;
     num_angle.clear(); angle_type.clear(); angle_a1.clear(); angle_a2.clear(); angle_a3.clear(); angle_style_name.clear();
@@ -2165,6 +2196,14 @@ void Engine::read_restart(const std::string &path) {
       } else if (tag == "PAIRSOFT") {
         int one; r.pod(one);
         pair_soft = one != 0;
+      } else if (tag == "SPRINGSELF") {
+        uint64_t ns; r.pod(ns);
+        if (ns < 1 || ns > (uint64_t)FORCEOP_MAX) throw LammpsError("Restart file is inconsistent");
+        for (uint64_t k = 0; k < ns; k++) {
+          std::string id;
+          r.str(id);
+          r.vec(restart_origins[id]);
+        }
       } else if (tag == "ANGLES") {
         r.pod(nangletypes); r.pod(extra_angle); r.pod(apa); r.pod(nangles);
         r.vec(num_angle); r.vec(angle_type); r.vec(angle_a1); r.vec(angle_a2); r.vec(angle_a3);
@@ -2175,6 +2214,7 @@ void Engine::read_restart(const std::string &path) {
   fclose(fp);
   if (x.size() != 3 * (size_t)natoms || num_bond.size() != (size_t)natoms) throw LammpsError("Restart file is inconsistent");
   if ((!gmask.empty() && gmask.size() != (size_t)natoms) || (apa && num_angle.size() != (size_t)natoms)) throw LammpsError("Restart file is inconsistent");
+  for (auto &o : restart_origins) if (o.second.size() != 3 * (size_t)natoms) throw LammpsError("Restart file is inconsistent");
   f.assign(3 * (size_t)natoms, 0.0);
   box_exist = true;
   host_current = true;
@@ -2185,6 +2225,13 @@ void Engine::read_restart(const std::string &path) {
 }
 
 void Engine::apply_restart_state(Fix *f) {
+  // fix spring/self specified again after read_restart: the origins of the file, not the positions of now (a fix of another
+  // style under the ID takes nothing and the entry is dropped, as Modify::restart_deallocate does)
+  auto ro = restart_origins.find(f->id);
+  if (ro != restart_origins.end()) {
+    if (auto *sp = dynamic_cast<FixSpringSelf *>(f)) sp->xorig = ro->second;
+    restart_origins.erase(ro);
+  }
   auto it = restart_fix_state.find(f->id);
   if (it == restart_fix_state.end()) return;
   const std::vector<unsigned char> &b = it->second;

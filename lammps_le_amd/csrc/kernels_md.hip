@@ -17,6 +17,7 @@
 #include "bin_inl.h"
 #include "soft_inl.h"
 #include <hip/hip_ext.h>
+#include <cstring>
 
 namespace lmp_le {
 
@@ -245,6 +246,12 @@ struct StepKernelArgs {
   const int *angle_n;
   const AngleTable *angles;
   double *partial;       // EF: block totals of energies and virial, rows of 16 as k_force<EFLAG> writes them
+  // EXT (behind everything the other variants read, whose offsets stay what they were): the run's force-op table (its entries
+  // hold the origin blocks), the image words [3][npad] in the order of pos, and the step's activity mask - bit k: entry k acts
+  // on the step whose forces this launch computes.  `gmask` above is set when an entry acts on a group other than all
+  const ForceOpTable *ext;
+  const int *img;
+  unsigned ext_active;
 };
 
 // reciprocal by v_rcp_f64 + two Newton steps (<= 1 ulp from the IEEE quotient 1/x; an IEEE divide is ~35 instructions)
@@ -725,6 +732,96 @@ __global__ __launch_bounds__(BLOCK) void k_wall(int n, const double4 *__restrict
   if (live) { fx[p] = f0; fy[p] = f1; fz[p] = f2; }
 }
 
+// ------------------------------------------------------------------------------------------
+// fix spring/self | addforce | setforce: the entries [k0, k1) of the run's table that belong to `phase` (0 before fix langevin or
+// without one, 1 behind it) and act on this step (`active`, bit k) applied to one bead, in table = fix order - setforce overwrites
+// what the entries before it left, the foriginal sums of addforce and setforce see it.  `gm`: the bead's group bits with bit 0
+// (all) set; `t`: its tag, which the origins go by.  Only a member of a tether, or of an addforce whose sums are wanted, reads its
+// three image words, and only a tether's member its origin.  Plain IEEE arithmetic in the reference's operation order (this file
+// is compiled without contraction): unwrap = x + image * prd (Domain::unmap), d = unwrap - origin, f -= K * d.
+// `acc` (EFLAG), ten columns that the caller keeps per entry: spring/self  K * |d|^2 (the host halves the sum);  addforce
+// -(f . unwrap), the force before the fix acted (3), f_a * unwrap_b xx yy zz xy xz yz;  setforce  the force before it acted (3)
+template <bool EFLAG>
+__device__ __forceinline__ void forceops_on_bead(const ForceOpTable *__restrict__ ft, int k0, int k1, int phase, unsigned active,
+                                                 const double4 &x, int gm, int t, const int *__restrict__ img, int npad, int p,
+                                                 const Box &box, double &f0, double &f1, double &f2, double *__restrict__ acc) {
+  double u0 = 0.0, u1 = 0.0, u2 = 0.0;
+  bool unwrapped = false;
+#pragma unroll 1
+  for (int k = k0; k < k1; k++) {
+    const ForceOpEntry &o = ft->e[k];
+    if (o.phase != phase || !((active >> k) & 1u) || !(gm & o.groupbit)) continue;
+    const int kind = o.kind;
+    if (!unwrapped && (kind == FORCEOP_SPRING || (EFLAG && kind == FORCEOP_ADD))) {
+      u0 = x.x + img[p] * box.prd[0];
+      u1 = x.y + img[npad + p] * box.prd[1];
+      u2 = x.z + img[2 * (size_t)npad + p] * box.prd[2];
+      unwrapped = true;
+    }
+    if (kind == FORCEOP_SPRING) {
+      const double *__restrict__ og = o.origin + t;
+      const size_t stride = (size_t)ft->stride;
+      double dx = u0 - og[0], dy = u1 - og[stride], dz = u2 - og[2 * stride];
+      const int m = o.mask;
+      if (!(m & 1)) dx = 0.0;
+      if (!(m & 2)) dy = 0.0;
+      if (!(m & 4)) dz = 0.0;
+      const double K = o.k;
+      f0 -= K * dx; f1 -= K * dy; f2 -= K * dz;
+      if (EFLAG) acc[0] += K * (dx * dx + dy * dy + dz * dz);
+    } else if (kind == FORCEOP_ADD) {
+      const double v0 = o.v[0], v1 = o.v[1], v2 = o.v[2];
+      if (EFLAG) {
+        acc[0] -= v0 * u0 + v1 * u1 + v2 * u2;
+        acc[1] += f0; acc[2] += f1; acc[3] += f2;
+        acc[4] += v0 * u0; acc[5] += v1 * u1; acc[6] += v2 * u2;
+        acc[7] += v0 * u1; acc[8] += v0 * u2; acc[9] += v1 * u2;
+      }
+      f0 += v0; f1 += v1; f2 += v2;
+    } else {
+      if (EFLAG) { acc[1] += f0; acc[2] += f1; acc[3] += f2; }
+      const int m = o.mask;
+      if (m & 1) f0 = o.v[0];
+      if (m & 2) f1 = o.v[1];
+      if (m & 4) f2 = o.v[2];
+    }
+  }
+}
+// the unfused post-force kernel of the three: the entries of one `phase` applied to f in table order; EFLAG: per entry the block
+// sums of the ten columns into rows of 16 (k_colsum<16> adds them up).  An entry that does not act on this step leaves its rows
+// as they are
+template <bool EFLAG>
+__global__ __launch_bounds__(BLOCK) void k_fixforce(int n, int npad, const double4 *__restrict__ pos, const int *__restrict__ tag,
+                                                    const int *__restrict__ gmask, const int *__restrict__ img, Box box,
+                                                    const ForceOpTable *__restrict__ ft, int phase, unsigned active,
+                                                    double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz,
+                                                    double *__restrict__ partial, int rows) {
+  const int p = blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = p < n;
+  double4 x = make_double4(0.0, 0.0, 0.0, 0.0);
+  double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+  int gm = 1, t = 0;
+  if (live) {
+    x = pos[p];
+    f0 = fx[p]; f1 = fy[p]; f2 = fz[p];
+    t = tag[p];
+    if (gmask) gm = gmask[t] | 1;
+  }
+  const int nk = ft->n;
+  for (int k = 0; k < nk; k++) {
+    if (ft->e[k].phase != phase || !((active >> k) & 1u)) continue;      // (the same for every lane of the grid)
+    double acc[FORCEOP_COLS];
+#pragma unroll
+    for (int c = 0; c < FORCEOP_COLS; c++) acc[c] = 0.0;
+    if (live) forceops_on_bead<EFLAG>(ft, k, k + 1, phase, active, x, gm, t, img, npad, p, box, f0, f1, f2, acc);
+    if (EFLAG) {
+      block_reduce_store<FORCEOP_COLS>(acc, partial + (size_t)k * rows * 16, blockIdx.x, 0);
+      __syncthreads();       // (the next entry reuses the reduction's LDS)
+    }
+  }
+  if (live) { fx[p] = f0; fy[p] = f1; fz[p] = f2; }
+}
+
 // forces only (setup, thermo steps, runs without the standard nve+langevin pair of fixes)
 // NOBOND: the bond entries at the head of the lists are skipped (run_style respa with pair and bond forces on different levels)
 template <bool EFLAG, bool HAS_PAIR, bool NOBOND = false, bool SOFT = false>
@@ -835,10 +932,12 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // WALL: fix wall/region on group all (wall_force): the walls defined before fix langevin add their force before drag and noise,
 // the ones behind it after - the order the reference's post_force hooks run in; the wall needs nothing but the bead's own
 // position, which is in registers here (four lanes per bead: lane 0, behind the butterfly)
+// EXT: fix spring/self, addforce, setforce (forceops_on_bead) at their place among the post-force fixes, as the walls; the bead's
+// group bits come by tag (not loaded when every entry is on group all), its images and origin only if it is a member
 // The parameters from `tag` on are the members of S and k_step's five direct pointers once more, __restrict__-qualified: the
 // loads of level 0 / level 1 below and of the AHEAD shapes move ahead of the stores into `flags` only with it (StepKernelArgs).
 // Read straight from S here, the members give 2 instantiations other VGPR counts and the wall variants vector loads of their table.
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL, bool SOFT>
+template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL, bool SOFT, bool EXT>
 __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt, const StepKernelArgs &S,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
@@ -866,7 +965,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   if (LAZYV) pv = vperm[p];
   double a = vx[pv], b = vy[pv], c = vz[pv];
   int t = 0;
-  if (LANGEVIN || GRP) t = tag[p];
+  if (LANGEVIN || GRP || EXT) t = tag[p];
   const BeadPre L = bead_preload<HAS_PAIR, LPB, AHEAD>(A, p, sub);
   double4 hold = ri;
   if (AHEAD && NEXT && check) hold = xhold[p];
@@ -879,6 +978,8 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     m_nve = nvebit == 1 || (gm & nvebit);
     m_lg = lgbit == 1 || (gm & lgbit);
   }
+  int gm_ext = 1;
+  if (EXT && gmask) gm_ext = gmask[t] | 1;
   if (LANGEVIN && !(DIAG && (A.diag & 4)) && (!GRP || m_lg)) {
     int rank = IDENT ? (t - 1) : crank[t];
     d0 = draws[3 * (size_t)rank]; d1 = draws[3 * (size_t)rank + 1]; d2 = draws[3 * (size_t)rank + 2];
@@ -901,6 +1002,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   // (a bead outside its region raises the error flag here, ahead of the `poisoned` test below: a launch that is discarded and
   //  repeated after a list overflow reports it one launch early, from the same positions the repeated launch reads)
   if (WALL) walls_on_bead(wt, 0, ri, f0, f1, f2, flags);
+  if (EXT) forceops_on_bead<false>(S.ext, 0, S.ext->n, 0, S.ext_active, ri, gm_ext, t, S.img, A.npad, p, box, f0, f1, f2, nullptr);
   if (LANGEVIN && (!GRP || m_lg)) {
     double gamma1 = tt.g1[type], gamma2 = tt.g2[type];
     const double inv = 1.0 / 16777216.0;
@@ -914,6 +1016,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     f2 += fdrag2 + fran2;
   }
   if (WALL && LANGEVIN) walls_on_bead(wt, 1, ri, f0, f1, f2, flags);
+  if (EXT && LANGEVIN) forceops_on_bead<false>(S.ext, 0, S.ext->n, 1, S.ext_active, ri, gm_ext, t, S.img, A.npad, p, box, f0, f1, f2, nullptr);
   if (poisoned) return;
   const double dtfm = tt.dtfm[type];
   if (!GRP || m_nve) { a += dtfm * f0; b += dtfm * f1; c += dtfm * f2; }          // final_integrate of this step
@@ -974,7 +1077,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   else { vx[p] = a; vy[p] = b; vz[p] = c; }
 }
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
-          bool GRP = false, bool LAZYV = false, bool WALL = false, bool SOFT = false>
+          bool GRP = false, bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false>
 __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
                                                                                            StepKernelArgs S, double *__restrict__ fx,
                                                                                            double *__restrict__ fy, double *__restrict__ fz,
@@ -987,6 +1090,8 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
                 "wall variant: the three plain shapes with a pair style");
   static_assert(!SOFT || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && (LPB == 1 || AHEAD)),
                 "soft variant: the three plain shapes with a pair style");
+  static_assert(!EXT || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && !SOFT && (LPB == 1 || AHEAD)),
+                "EXT variant: the three plain shapes with a pair style");
   static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
                 "velocity hand-over: the throughput shape only");
   static_assert(!EF || (!NEXT && LPB == 1), "energy variant: NEXT = false, one lane per bead");
@@ -1003,7 +1108,7 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT>(
+  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT, EXT>(
       A, bt, box, tt, S, s_tab, s_bt, S.tag, S.ranks, S.draws, S.vx, S.vy, S.vz, fx, fy, fz, pos_next, xhold, S.dtv, S.triggersq, S.check, S.flags,
       S.phase, S.which, e, kev[0], S.gmask, S.nvebit, S.lgbit, S.vperm, S.vxo, S.vyo, S.vzo, S.walls);
   if (EF) {
@@ -1198,10 +1303,23 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
       hipLaunchKernelGGL((k_force<E, P, NOBOND, SOFT>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
   }, eflag, (parts & 1) != 0, parts == 1, soft && (parts & 1) != 0);
 }
-// f(k_step<the plan's twelve template arguments, lazy_v as LAZYV before the last two>); false: there is no such instantiation
+// f(k_step<the plan's thirteen template arguments, lazy_v as LAZYV before the last three>); false: there is no such instantiation
 template <class F>
 static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
+  if (p.ext) {
+    // the EXT variants differ in five flags only; a fourteenth flag in the enumeration below would double what the host
+    // compiler has to expand (2^13 -> 2^14 bodies)
+    if (!p.pair || p.diag || p.ang || p.ef || p.grp || lazy_v || p.wall || p.soft) return false;
+    with_flags([&](auto L, auto N, auto I, auto W4, auto H) {
+      constexpr int W = W4 ? 4 : 1;
+      if constexpr (step_variant_exists(L, N, I, true, W, false, H, false, false, false, false, false, false, true)) {
+        f(k_step<L, N, I, true, W, false, H, false, false, false, false, false, false, true>);
+        found = true;
+      }
+    }, p.langevin, p.next, p.ident, p.lpb == 4, p.ahead);
+    return found;
+  }
   with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z, auto WL, auto SF) {
     constexpr int W = W4 ? 4 : 1;
     if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL, SF)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL, SF>); found = true; }
@@ -1229,6 +1347,12 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
   if (p.wall) {
     if (!d.walltab_dev) throw LammpsError("internal: fused wall step without the wall table");
     S.walls = d.walltab_dev;
+  }
+  if (p.ext) {
+    if (!d.forceoptab_dev) throw LammpsError("internal: fused EXT step without the force-op table");
+    if (d.forceop_grouped && !d.gmask) throw LammpsError("internal: fused EXT step on groups without group masks");
+    S.ext = d.forceoptab_dev; S.img = d.img; S.ext_active = a.ext_active;
+    if (d.forceop_grouped) S.gmask = d.gmask;
   }
   // a whole step of a run with an angle style (NEXT) evaluates the listed angles inside the kernel
   if (p.ang && p.next) {
@@ -1292,16 +1416,18 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
 // check, cells, walls (StepRequest::walls); out = fused, the plan's first ten template arguments in k_step's order (langevin
 // ... grp), bin, member_ranks, diag_bits, lds_pad, whether the dispatcher of launch_step holds the instantiation the plan names
 // (its own look-up, nothing is launched), then [16] = StepPlan::wall and [17] = the plan takes velocities a rebuild left pending
-static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out, int soft = 0, int *out_soft = nullptr) {
+static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out, int soft = 0, int *out_soft = nullptr,
+                           int ext = 0, int *out_ext = nullptr) {
   StepRequest r;
   r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
-  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0;
+  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0; r.ext = ext != 0;
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
   const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
   const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
                      p.diag_bits, (int)p.lds_pad, known, p.wall, takes_pending_v(p, decomposed != 0)};
   for (int k = 0; k < 18; k++) out[k] = v[k];
   if (out_soft) *out_soft = p.soft;
+  if (out_ext) *out_ext = p.ext;
 }
 // eleven inputs (no walls), the first 16 outputs
 extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
@@ -1316,6 +1442,13 @@ extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, cons
 // thirteen inputs, req[11] = walls, req[12] = pair_style soft; the 18 outputs of the hook above, then [18] = StepPlan::soft
 extern "C" void lammps_le_test_step_plan_soft(int n_owned, int decomposed, const int *req, int *out) {
   test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18);
+}
+
+// fourteen inputs, req[11] = walls, req[12] = pair_style soft, req[13] = fix spring/self | addforce | setforce; the 19 outputs of
+// the hook above, then [19] = StepPlan::ext and [20] = count_step_variants(), the number of instantiations the dispatchers hold
+extern "C" void lammps_le_test_step_plan_ext(int n_owned, int decomposed, const int *req, int *out) {
+  test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19);
+  out[20] = count_step_variants();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1562,6 +1695,67 @@ void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out) {
   }
   stream_sync(d);
   for (int k = 0; k < 16 * wt.n; k++) out[k] = d.partial_h[k];
+}
+
+void upload_forceop_table(DeviceState &d, ForceOpTable &ft, const double *const *origins, int natoms) {
+  const size_t stride = (size_t)natoms + 1;
+  ft.stride = (int)stride;
+  d.forceop_grouped = false;
+  std::vector<double> block(3 * stride);
+  for (int k = 0; k < ft.n; k++) {
+    if (ft.e[k].groupbit != 1) d.forceop_grouped = true;
+    ft.e[k].origin = nullptr;
+    if (!origins[k]) continue;
+    // [natoms][3] by tag - 1 on the host -> [3][natoms + 1] by tag here
+    for (int c = 0; c < 3; c++) {
+      block[c * stride] = 0.0;
+      for (int i = 0; i < natoms; i++) block[c * stride + i + 1] = origins[k][3 * (size_t)i + c];
+    }
+    DEV_RESERVE(d.mem, d.forceop_origin[k], 3 * stride);
+    HIP_CHECK(hipMemcpyAsync(d.forceop_origin[k], block.data(), 3 * stride * sizeof(double), hipMemcpyHostToDevice, d.stream));
+    HIP_CHECK(hipStreamSynchronize(d.stream));      // (`block` is filled again for the next entry)
+    ft.e[k].origin = d.forceop_origin[k];
+  }
+  DEV_RESERVE(d.mem, d.forceoptab_dev, 1);
+  const size_t np = (size_t)FORCEOP_MAX * (d.nred_blocks + 1) * 16;
+  // the rows of block sums outlive a `run` while they still mean the same: an addforce with `every N` that skips the setup step
+  // of the next run reports the sums of the last step on which it acted, as the reference keeps foriginal.  Another table (the
+  // origin addresses aside), another bead count or a new buffer starts from zero
+  ForceOpTable same = ft;
+  for (int k = 0; k < FORCEOP_MAX; k++) same.e[k].origin = nullptr;
+  const bool fresh = DEV_RESERVE(d.mem, d.forceop_partial, np);
+  if (fresh || d.forceop_rows_n != d.n || memcmp(&same, &d.forceoptab_last, sizeof(ForceOpTable)) != 0)
+    HIP_CHECK(hipMemsetAsync(d.forceop_partial, 0, np * sizeof(double), d.stream));
+  d.forceoptab_last = same;
+  d.forceop_rows_n = d.n;
+  HIP_CHECK(hipMemcpyAsync(d.forceoptab_dev, &ft, sizeof(ForceOpTable), hipMemcpyHostToDevice, d.stream));
+  HIP_CHECK(hipStreamSynchronize(d.stream));      // (`ft` is the caller's object)
+}
+void launch_fixforce(DeviceState &d, const ForceOpTable &ft, int phase, unsigned active, bool eflag) {
+  bool any = false;
+  for (int k = 0; k < ft.n; k++) if (ft.e[k].phase == phase && ((active >> k) & 1u)) any = true;
+  if (!any) return;
+  if (!d.forceoptab_dev || !d.forceop_partial) throw LammpsError("internal: fix spring/self | addforce | setforce without the table on the device");
+  if (d.forceop_grouped && !d.gmask) throw LammpsError("internal: fix spring/self | addforce | setforce on a group without group masks");
+  if (ft.stride != d.maxtag + 1) throw LammpsError("internal: the origin blocks do not match the atom count");
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  if (nb > d.nred_blocks) throw LammpsError("internal: more blocks than rows of block sums");
+  with_flags([&](auto E) {
+    hipLaunchKernelGGL((k_fixforce<E>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.npad, d.pos, d.tag,
+                       d.forceop_grouped ? d.gmask : (const int *)nullptr, d.img, d.box, d.forceoptab_dev, phase, active,
+                       d.f[0], d.f[1], d.f[2], d.forceop_partial, d.nred_blocks + 1);
+  }, eflag);
+}
+void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *out) {
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  const size_t rows = (size_t)d.nred_blocks + 1;
+  for (int k = 0; k < ft.n; k++) {
+    double *tab = d.forceop_partial + (size_t)k * rows * 16;
+    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+    HIP_CHECK(hipMemcpyAsync(d.partial_h + 16 * (size_t)k, tab + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+  }
+  stream_sync(d);
+  for (int k = 0; k < 16 * ft.n; k++) out[k] = d.partial_h[k];
 }
 
 // sum the per-block partials in a fixed order (deterministic); the totals land in the table's spare row nb

@@ -31,13 +31,14 @@ struct StepKnobs {
 // angle style is active; thermo: thermo output after this step, energies and virial are wanted; check: the displacement test
 // of Neighbor::check_distance is due; cells: the cell tables the binning writes are allocated; walls: fix wall/region - 0 none,
 // 1 walls the step kernel can take (every one on group all), 2 walls that force the unfused kernels (one of them on a group);
-// soft: the pair style is soft, not lj/cut (pair is set as well)
+// soft: the pair style is soft, not lj/cut (pair is set as well); ext: fix spring/self, addforce or setforce act (on any group)
 struct StepRequest {
   bool langevin = false, next = false, ident = false, pair = false, angles = false, thermo = false, check = false, cells = false;
   int nvebit = 1, lgbit = 1; // group bits of fix nve / fix langevin (1 = all)
   int which = -1;            // decomposed runs with halo / compute overlap: the phase this launch handles (-1: every bead)
   int walls = 0;
   bool soft = false;
+  bool ext = false;
 };
 
 struct StepPlan {
@@ -48,6 +49,7 @@ struct StepPlan {
   bool diag = false, ahead = false, ang = false, ef = false, grp = false;
   bool wall = false;         // fix wall/region evaluated inside the kernel (wall_force)
   bool soft = false;         // pair_style soft: the soft functor of pair_term
+  bool ext = false;          // fix spring/self | addforce | setforce evaluated inside the kernel (forceops_on_bead)
   bool bin = false;          // positions binned by this launch
   bool member_ranks = false; // the draws go by the rank among the members of fix langevin's group, not by the canonical rank
   int diag_bits = 0;         // != 0: the diagnostic launch <true, true, true, true, 1, DIAG> goes first, with these parts switched off
@@ -78,6 +80,13 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
     if (!r.pair || r.walls || p.grp || r.thermo || r.angles) return unfused;
     p.soft = true;
   }
+  if (r.ext) {
+    // fix spring/self | addforce | setforce: the EXT variant covers what the wall variant covers - plain steps with a pair style,
+    // no angle style, no fix nve / langevin on a group - and not together with walls or pair_style soft; the fixes' own groups
+    // are tested inside the kernel.  Thermo steps (the fixes' sums) and everything else take k_fixforce
+    if (!r.pair || r.walls || r.soft || p.grp || r.thermo || r.angles) return unfused;
+    p.ext = true;
+  }
   if (p.grp) {
     // fix nve / fix langevin on a group: one lane per bead, ranks from a table; with an angle style only the throughput shape
     // (the look-ahead shape of small systems has no group + angle instantiation); thermo steps take the unfused kernels
@@ -100,14 +109,15 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   // positions binned by this launch: single GPU, whole-step launch with a displacement test in it, one lane per bead (with
   // four lanes per bead - small systems - it was measured slower than the separate k_wrap_bin: 62.2k vs 64.5k steps/s at 32k)
   p.bin = p.check && p.next && !decomposed && r.which < 0 && p.lpb != 4 && !k.no_fused_bin && r.cells;
-  if (k.diag_step && r.langevin && r.next && r.ident && r.pair && r.which < 0 && p.lpb != 4 && !p.ef && !p.wall && !p.soft) p.diag_bits = k.diag_step;
+  if (k.diag_step && r.langevin && r.next && r.ident && r.pair && r.which < 0 && p.lpb != 4 && !p.ef && !p.wall && !p.soft && !p.ext) p.diag_bits = k.diag_step;
   return p;
 }
 
-// The instantiations of k_step that exist, by its thirteen template arguments (what plan_step plans with; implies the five
-// static_asserts inside k_step): 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 129
+// The instantiations of k_step that exist, by its fourteen template arguments (what plan_step plans with; implies the six
+// static_asserts inside k_step): 24 + 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 153
 constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
-                                   bool LAZYV = false, bool WALL = false, bool SOFT = false) {
+                                   bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false) {
+  if (EXT) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && !SOFT && (LPB == 1 || AHEAD);   // spring/self, addforce, setforce inside the step: L, N, I x three shapes = 24
   if (SOFT) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && (LPB == 1 || AHEAD);   // pair_style soft inside the step: L, N, I x three shapes = 24
   if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region inside the step: L, N, I x three shapes = 24
   if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
@@ -119,17 +129,17 @@ constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool
 }
 constexpr int count_step_variants() {
   int c = 0;
-  for (int m = 0; m < 8192; m++)
-    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048, m & 4096);
+  for (int m = 0; m < 16384; m++)
+    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048, m & 4096, m & 8192);
   return c;
 }
-static_assert(count_step_variants() == 129, "the set of k_step instantiations changed");
+static_assert(count_step_variants() == 153, "the set of k_step instantiations changed");
 
 // The launch of this plan takes the velocities a rebuild left in the old order (DeviceState::v_pending): the throughput shape
 // of the kernel, in one launch over every bead of one GPU, with no diagnostic launch in front of it.  Engine::iterate asks
 // before it lets a rebuild leave them, launch_step when it picks the instantiation.
 inline bool takes_pending_v(const StepPlan &p, bool decomposed) {
-  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall, p.soft) &&
+  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall, p.soft, p.ext) &&
          p.which < 0 && !p.diag_bits && !decomposed;
 }
 
