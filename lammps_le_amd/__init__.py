@@ -30,6 +30,13 @@ LMP_STYLE_GLOBAL, LMP_STYLE_ATOM, LMP_STYLE_LOCAL = range(3)
 LMP_TYPE_SCALAR, LMP_TYPE_VECTOR, LMP_TYPE_ARRAY, LMP_SIZE_VECTOR, LMP_SIZE_ROWS, LMP_SIZE_COLS = range(6)
 
 
+# lammps_le_stat "min_stop" indexes these: the reference's Min::stopstrings, as the engine prints them in its stats block (the
+# tests read the printed text back through this table, so the two cannot drift apart unnoticed)
+MIN_STOP_STRINGS = ("max iterations", "max force evaluations", "energy tolerance", "force tolerance", "search direction is not downhill",
+                    "linesearch alpha is zero", "forces are zero", "quadratic factors are zero", "trust region too small",
+                    "HFTN minimizer error", "walltime limit reached", "max iterations with v.f negative")
+
+
 def library_path():
     return _SO
 
@@ -371,6 +378,14 @@ class lammps(object):
 
     def stat(self, name):
         return self.lib.lammps_le_stat(self.lmp, name.encode())
+
+    def minimize(self, etol, ftol, maxiter, maxeval):
+        """`minimize etol ftol maxiter maxeval` (min_style cg | sd on the device) -> what the stats block prints: the stop
+        criterion as text, iterations, force evaluations, the three energies, the final force norms and the last alpha."""
+        self.command("minimize %.17g %.17g %d %d" % (etol, ftol, maxiter, maxeval))
+        return dict(stop=MIN_STOP_STRINGS[int(self.stat("min_stop"))], iterations=int(self.stat("min_iterations")), evals=int(self.stat("min_evals")),
+                    e_initial=self.stat("min_e_initial"), e_previous=self.stat("min_e_previous"), e_final=self.stat("min_e_final"),
+                    fnorm=self.get_thermo("fnorm"), fmax=self.get_thermo("fmax"), alpha=self.stat("min_alpha"))
 
     def thermo_history(self):
         """Every thermo line printed so far: array of rows (step, temp, epair, emol, etotal, press, bonds)."""

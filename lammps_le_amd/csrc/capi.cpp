@@ -831,6 +831,22 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "steps_fused_wall") return (double)e->steps_fused_wall;      // of steps_fused: fix wall/region inside the step kernel
   if (k == "steps_fused_soft") return (double)e->steps_fused_soft;      // of steps_fused: pair_style soft inside the step kernel
   if (k == "pair_table_copies") return (double)e->pair_table_copies;    // fix adapt: copies of the pair table in the middle of runs
+  // the last `minimize`: iterations, force evaluations, index into Min::stopstrings, the last line search's alpha, times the host
+  // waited for the device, list builds; and the numbers of its stats block
+  if (k == "min_iterations") return (double)e->min_niter;
+  if (k == "min_evals") return (double)e->min_neval;
+  if (k == "min_stop") return (double)e->min_stop;
+  if (k == "min_alpha") return e->min_alpha;
+  if (k == "min_host_waits") return (double)e->min_host_waits;
+  if (k == "min_rebuilds") return (double)e->min_rebuilds;
+  if (k == "min_e_initial") return e->min_einitial;
+  if (k == "min_e_previous") return e->min_eprevious;
+  if (k == "min_e_final") return e->min_efinal;
+  if (k == "min_fnorm_initial") return e->min_fnorm2_init;
+  if (k == "min_fnorm_final") return e->min_fnorm2_final;
+  if (k == "min_fmax_initial") return e->min_fnorminf_init;
+  if (k == "min_fmax_final") return e->min_fnorminf_final;
+  if (k == "host_waits") return e->dev ? (double)e->dev->host_waits : 0.0;
   if (k == "neigh_time" || k == "time_neigh") return e->timers[Engine::T_NEIGH];
   if (k == "time_pair") return e->timers[Engine::T_PAIR];
   if (k == "time_bond") return e->timers[Engine::T_BOND];

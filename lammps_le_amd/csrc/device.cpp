@@ -231,6 +231,7 @@ __global__ void k_publish_flags(int *__restrict__ flags, int *__restrict__ host,
   if (k == 0) __hip_atomic_store(&host[FLAG_SEQ_SLOT], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 void stream_sync(DeviceState &d) {
+  d.host_waits++;
   if (d.comm_watch) d.comm_watch->wait_stream(d.stream);
   else HIP_CHECK(hipStreamSynchronize(d.stream));
 }
@@ -253,7 +254,7 @@ void wait_flags(DeviceState &d) {
     while (h[FLAG_SEQ_SLOT] != seq) {
       if ((++it & 0xFFF) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(50)) break;   // long-running
     }                                                                            // work (or a fault): block instead
-    if (h[FLAG_SEQ_SLOT] == seq) { std::atomic_thread_fence(std::memory_order_acquire); return; }   // pairs with the release store
+    if (h[FLAG_SEQ_SLOT] == seq) { std::atomic_thread_fence(std::memory_order_acquire); d.host_waits++; return; }   // pairs with the release store
   }
   stream_sync(d);
 }

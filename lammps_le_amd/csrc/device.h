@@ -373,9 +373,27 @@ struct DeviceState {
   char *local_scan_tmp = nullptr;
   char *local_rows = nullptr;       // [R][6] doubles (PAIR kind), then [R][4] ints
   char *local_rows_h = nullptr;     // pinned
+  // ---- minimize (kernels_min.hip): x0, g, h by tag [3][maxtag + 2], allocated by `minimize` and released at its end; the block
+  // partials of the dot products; the record of one evaluation in mapped host memory (the last two also serve fmax / fnorm) ----
+  double *min_x0 = nullptr, *min_g = nullptr, *min_h = nullptr;
+  double *min_partial = nullptr;    // [blocks + 1][MIN_DOT_COLS]
+  double *min_rec = nullptr;        // [MIN_REC_MAX] pinned, mapped
+  double *min_rec_dev = nullptr;    // its device-side address (a view)
+  long host_waits = 0;              // times the host waited for the stream or a flag publish (lammps_le_stat "min_host_waits" is a difference)
   // owns every pointer (but the mapped peer windows), stream and event above.  The LAST member: destroyed first, while the
   // fields its records point at are still there
   DevMem mem;
+};
+
+// minimize: the columns of a dots pass (the first MIN_NSUM are sums, the others maxima), the record's capacity and the
+// totals of other reductions that travel with it (each `len` doubles in device memory, appended behind the dots)
+enum MinDotCol { MIN_FF = 0, MIN_FH = 1, MIN_FG = 2, MIN_FMAX2 = 3, MIN_FMAXC = 4, MIN_HMAXC = 5 };
+constexpr int MIN_NSUM = 3, MIN_DOT_USED = 6, MIN_DOT_COLS = 8, MIN_REC_MAX = 256, MIN_SRC_MAX = 16;
+struct MinSources {
+  int n = 0;
+  const double *ptr[MIN_SRC_MAX] = {nullptr};
+  int len[MIN_SRC_MAX] = {0};
+  void add(const double *p, int l) { if (n >= MIN_SRC_MAX) throw LammpsError("internal: too many sources for the minimiser's record"); ptr[n] = p; len[n++] = l; }
 };
 
 // with_flags(f, a, b, ...) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...): where the launchers turn run-time
@@ -439,6 +457,25 @@ void launch_fixforce(DeviceState &d, const ForceOpTable &ft, int phase, unsigned
 void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *out);
 // reductions: returns sums of `partial` columns on the host (synchronises the stream)
 void reduce_partials(DeviceState &d, double *out16);
+
+// the same sums left in device memory without a copy or a wait (the totals land in the spare row of each table): where they
+// are, for a record that collects them (kernels_min.hip k_min_collect)
+void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, bool angles, MinSources &src);
+
+// minimize (kernels_min.hip).  min_alloc: the partials and the record, with `vectors` also x0 g h; min_free releases the
+// vectors and, with `all`, the rest.
+// launch_min_move raises FLAG_MOVED by the rule of k_initial_integrate; launch_min_dots fills the block partials of a dots
+// pass (with_g / with_h: the vectors exist and are read); launch_min_direction those of g.h and max |h| (cg) or sets h = f (sd);
+// launch_min_collect adds the partials up (dots) and writes them and the sources into d.min_rec: valid after the next wait
+void min_alloc(DeviceState &d, bool vectors);
+void min_free(DeviceState &d, bool all);
+void launch_min_store(DeviceState &d);
+void launch_min_move(DeviceState &d, double alpha, double triggersq);
+void launch_min_reset_coords(DeviceState &d);
+void launch_min_dots(DeviceState &d, bool with_g, bool with_h);
+void launch_min_direction(DeviceState &d, bool cg, double beta);
+void launch_min_h_is_g(DeviceState &d);
+void launch_min_collect(DeviceState &d, bool dots, const MinSources &src);
 
 // neighbor (kernels_neigh.hip, kernels_dd.hip): the stages of a rebuild in the order Engine::reneighbor runs them; each
 // launches what the plan says (rebuild_plan.h).  Decomposed runs: rebuild_migrate (ownership; returns the slots to bin and

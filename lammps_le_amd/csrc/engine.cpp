@@ -1057,6 +1057,39 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
   if (nwall) reduce_wall_partials(d, walltab, s + 16);
   if (nops) reduce_fixforce_partials(d, forceoptab, s + 16 + 16 * nwall);
   if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * (nwall + nops));
+  double a8[8], k6[6];
+  const bool ang = angles_active();
+  if (ang) {
+    reduce_angle_partials(d, a8);
+    if (world > 1) comm->allreduce_host_sum(a8, 8);
+  }
+  if (want_ptensor) {
+    ke_tensor(d, tt, k6);
+    if (world > 1) comm->allreduce_host_sum(k6, 6);
+  }
+  ThermoRow r = thermo_from_sums(s, ang ? a8 : nullptr, want_ptensor ? k6 : nullptr);
+  if (want_fnorm) {            // Thermo::compute_fmax / compute_fnorm: one pass over the forces, block partials in a fixed order
+    min_alloc(d, false);
+    launch_min_dots(d, false, false);
+    launch_min_collect(d, true, MinSources());
+    stream_sync(d);
+    double m2[2] = {d.min_rec[MIN_FF], d.min_rec[MIN_FMAXC]};
+    if (world > 1) {
+      comm->allreduce_host_sum(m2, 1);
+      std::vector<double> all(world);
+      comm->allgather_host(&m2[1], all.data(), sizeof(double));
+      m2[1] = *std::max_element(all.begin(), all.end());
+    }
+    r.fnorm = std::sqrt(m2[0]);
+    r.fmax = m2[1];
+  }
+  sync_flags(d);
+  check_device_error(this, d);
+  return r;
+}
+
+ThermoRow Engine::thermo_from_sums(const double *s, const double *a8, const double *k6) {
+  const int nwall = walltab.n, nops = forceoptab.n;
   double efix = 0.0, vfix[6] = {0, 0, 0, 0, 0, 0};      // Modify::thermo_energy (src/compute_pe.cpp:102), the fixes of compute_pressure.cpp:201-220
   for (int k = 0; k < nwall; k++) {
     FixWallRegion *w = wall_fixes[k];
@@ -1086,10 +1119,7 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
   double ke = r.temp * 0.5 * dof * boltz;
   r.evdwl = s[0]; r.ebond = s[1];
   for (int k = 0; k < 6; k++) r.virial[k] = s[2 + k] + s[8 + k];
-  if (angles_active()) {       // thermo's emol = ebond + eangle (src/thermo.cpp), the pressure's virial includes the angles'
-    double a8[8];
-    reduce_angle_partials(d, a8);
-    if (world > 1) comm->allreduce_host_sum(a8, 8);
+  if (a8) {                    // thermo's emol = ebond + eangle (src/thermo.cpp), the pressure's virial includes the angles'
     r.eangle = a8[0];
     for (int k = 0; k < 6; k++) r.virial[k] += a8[1 + k];
   }
@@ -1102,15 +1132,10 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
   r.ke = ke / norm;
   r.etotal = (ke + r.evdwl + emol + efix) / norm;
   r.nbonds = nbonds;
-  if (want_ptensor) {          // (ke_tensor[i] + virial[i]) / volume * nktv2p, src/compute_pressure.cpp:244-290
-    double k6[6];
-    ke_tensor(d, tt, k6);
-    if (world > 1) comm->allreduce_host_sum(k6, 6);
+  if (k6) {                    // (ke_tensor[i] + virial[i]) / volume * nktv2p, src/compute_pressure.cpp:244-290
     for (int k = 0; k < 6; k++) r.ptensor[k] = (k6[k] * mvv2e + r.virial[k]) / vol * nktv2p;
     r.has_ptensor = true;
   }
-  sync_flags(d);
-  check_device_error(this, d);
   return r;
 }
 
@@ -1151,6 +1176,10 @@ bool Engine::thermo_keyword(const ThermoRow &r, const std::string &k, double &va
     val = 0.0;
     for (int c = 0; c < 6; c++) if (k == names[c]) val = r.ptensor[c];
   }
+  else if (k == "fmax" || k == "fnorm") {                                            // src/thermo.cpp compute_fmax / compute_fnorm
+    want_fnorm = true;         // (from the next thermo evaluation on, like the pressure tensor)
+    val = k == "fmax" ? r.fmax : r.fnorm;
+  }
   else if (k == "bonds") { val = (double)nbonds; isint = true; }     // (atom->nbonds at the time of the call, src/thermo.cpp:1996-1999)
   else if (k == "angles") { val = (double)nangles; isint = true; }
   else if (k == "dihedrals" || k == "impropers") { val = 0.0; isint = true; }
@@ -1183,7 +1212,7 @@ static const char *thermo_title(const std::string &k) {       // column titles: 
       {"etail", "E_tail"}, {"vol", "Volume"}, {"density", "Density"}, {"lx", "Lx"}, {"ly", "Ly"}, {"lz", "Lz"}, {"xlo", "Xlo"},
       {"xhi", "Xhi"}, {"ylo", "Ylo"}, {"yhi", "Yhi"}, {"zlo", "Zlo"}, {"zhi", "Zhi"}, {"xy", "Xy"}, {"xz", "Xz"}, {"yz", "Yz"},
       {"pxx", "Pxx"}, {"pyy", "Pyy"}, {"pzz", "Pzz"}, {"pxy", "Pxy"}, {"pxz", "Pxz"}, {"pyz", "Pyz"}, {"bonds", "Bonds"}, {"angles", "Angles"}, {"dihedrals", "Diheds"}, {"impropers", "Impros"}, {"nbuild", "Nbuild"},
-      {"ndanger", "Ndanger"}};
+      {"ndanger", "Ndanger"}, {"fmax", "Fmax"}, {"fnorm", "Fnorm"}};
   for (auto &n : names) if (k == n[0]) return n[1];
   return nullptr;
 }
@@ -1217,6 +1246,7 @@ void Engine::print_thermo(const ThermoRow &r) {
       if (isint) snprintf(buf, sizeof buf, "%-8s = %14ld ", t ? t : k.c_str(), (long)val);
       else snprintf(buf, sizeof buf, "%-8s = %14.4f ", t ? t : k.c_str(), val);
     } else if (isint) snprintf(buf, sizeof buf, "%8ld ", (long)val);
+    else if (!thermo_float_format.empty()) snprintf(buf, sizeof buf, (thermo_float_format + " ").c_str(), val);
     else snprintf(buf, sizeof buf, "%12.8g ", val);
     line += buf;
     col++;
@@ -1607,65 +1637,12 @@ void Engine::run(long nsteps) {
   double tr0 = wall();
   init();
   build_forceop_table();      // (beside build_wall_table below, but ahead of the upload: what it refuses needs no device)
-  rebuild_knobs = RebuildKnobs();
   double tr1 = wall();
-  // (the fixes on groups are not those of the last upload: the masks, the member ranks and the thermostat's member count travel
-  // with an upload - also when the last fix on a group has gone and they have to fall back to `all`)
-  if (dev && dev_current && group_sig != group_signature()) { download(); dev_current = false; }
-  // (so are the cell grid and the lists for the cutoff of the last upload: another pair style or cutoff on the same handle)
-  char psig[96];
-  snprintf(psig, sizeof psig, "%s %.17g", pair_style_name(), cutneighmax);
-  if (dev && dev_current && pair_sig != psig) { download(); dev_current = false; }
-  pair_sig = psig;
-  if (!dev_current || !dev || !dev->pos) upload();
-  else push_pair_table(false);       // coefficients given since the last run
-  group_sig = group_signature();
-  build_wall_table();
-  // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
-  //  region ends every rank - the error flag travels with the displacement test's reduction, Engine::decide)
-  if (walltab.n) upload_wall_table(*dev, walltab);
-  // fix spring/self | addforce | setforce: the table (built above) and the origin blocks of the tethers (by tag, whole on every rank)
-  if (forceoptab.n) {
-    std::vector<const double *> origins;
-    for (auto *o : forceop_fixes) origins.push_back(o->kind == FORCEOP_SPRING ? o->xorig.data() : nullptr);
-    upload_forceop_table(*dev, forceoptab, origins.data(), natoms);
-  }
-  if (dev->dd) dd_fast_halo_switch(*dev);
-  for (int k = 1; k <= 3; k++) dev->sflag[k] = special_flag(k);
-  set_xhold_alias(*dev, !dev->dd && !rebuild_knobs.no_xhold_alias);
-  dev->scan_two_pass = rebuild_knobs.scan_two_pass;
-  dev->ident_order = local_order_is_tag_order();
-  {
-    // bond partner images: frozen at the reneighbor as in the reference (src/ntopo_bond_all.cpp:52-73), unless the minimum
-    // image of every step is provably the same thing (device.h bond_minimg)
-    double r0max = 0.0;
-    bool all_fene = nbondtypes > 0;
-    for (int b = 1; b <= nbondtypes; b++) {
-      if (bondtab.style[b] == 1) r0max = std::max(r0max, bondtab.p1[b]);
-      else if (bondtab.style[b] != 0) all_fene = false;
-    }
-    const double halfmin = 0.5 * std::min({box.prd[0], box.prd[1], box.prd[2]});
-    dev->bond_minimg = (all_fene && 2.0 * r0max * 1.000001 < halfmin && !rebuild_knobs.freeze_images) ? 1 : 0;
-  }
-  dev->newton_pair = newton_pair ? 1 : 0;
-  for (int k = 0; k < 3; k++) {
-    const double binsize_optimal = cutneighmax > 0.0 ? 0.5 * cutneighmax : box.prd[0];
-    int nb = (int)(box.prd[k] * (1.0 / binsize_optimal));
-    if (nb == 0) nb = 1;
-    dev->ref_nbin[k] = nb;
-    dev->ref_bininv[k] = 1.0 / (box.prd[k] / nb);
-  }
+  begin_run_state();
   double tr2 = wall();
-  le_reneigh_step.assign(fixes.size(), -1);
-  dev->le_snapshot = 0;
-  for (auto &f : fixes) if (f->force_reneighbor) dev->le_snapshot = 1;
-  note_topology_changed(*dev);     // bond tables may have been edited between runs
-  dev_edits_at_run = dev_edits;    // (the setup rebuild refreshes every ghost)
   beginstep = ntimestep;
   endstep = ntimestep + nsteps;
   atimestep = ntimestep;            // Integrate::init (src/integrate.cpp:48)
-  halo_step = -1;
-  host_current = false;
   double t0 = 0.0;
   struct InRun { bool &f; InRun(bool &b) : f(b) { f = true; } ~InRun() { f = false; } } in_run_guard(in_run);
   try {
@@ -1713,6 +1690,64 @@ void Engine::run(long nsteps) {
     snprintf(buf, sizeof buf, "FENE bond too long warnings: %d", dev->flags_h[FLAG_FENE_WARN]);
     warning(buf);
   }
+}
+
+// What `run` and `minimize` share between init() and their setup (the caller has built the table of the force fixes)
+void Engine::begin_run_state() {
+  rebuild_knobs = RebuildKnobs();
+  // (the fixes on groups are not those of the last upload: the masks, the member ranks and the thermostat's member count travel
+  // with an upload - also when the last fix on a group has gone and they have to fall back to `all`)
+  if (dev && dev_current && group_sig != group_signature()) { download(); dev_current = false; }
+  // (so are the cell grid and the lists for the cutoff of the last upload: another pair style or cutoff on the same handle)
+  char psig[96];
+  snprintf(psig, sizeof psig, "%s %.17g", pair_style_name(), cutneighmax);
+  if (dev && dev_current && pair_sig != psig) { download(); dev_current = false; }
+  pair_sig = psig;
+  if (!dev_current || !dev || !dev->pos) upload();
+  else push_pair_table(false);       // coefficients given since the last run
+  group_sig = group_signature();
+  build_wall_table();
+  // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
+  //  region ends every rank - the error flag travels with the displacement test's reduction, Engine::decide)
+  if (walltab.n) upload_wall_table(*dev, walltab);
+  // fix spring/self | addforce | setforce: the table (built above) and the origin blocks of the tethers (by tag, whole on every rank)
+  if (forceoptab.n) {
+    std::vector<const double *> origins;
+    for (auto *o : forceop_fixes) origins.push_back(o->kind == FORCEOP_SPRING ? o->xorig.data() : nullptr);
+    upload_forceop_table(*dev, forceoptab, origins.data(), natoms);
+  }
+  if (dev->dd) dd_fast_halo_switch(*dev);
+  for (int k = 1; k <= 3; k++) dev->sflag[k] = special_flag(k);
+  set_xhold_alias(*dev, !dev->dd && !rebuild_knobs.no_xhold_alias);
+  dev->scan_two_pass = rebuild_knobs.scan_two_pass;
+  dev->ident_order = local_order_is_tag_order();
+  {
+    // bond partner images: frozen at the reneighbor as in the reference (src/ntopo_bond_all.cpp:52-73), unless the minimum
+    // image of every step is provably the same thing (device.h bond_minimg)
+    double r0max = 0.0;
+    bool all_fene = nbondtypes > 0;
+    for (int b = 1; b <= nbondtypes; b++) {
+      if (bondtab.style[b] == 1) r0max = std::max(r0max, bondtab.p1[b]);
+      else if (bondtab.style[b] != 0) all_fene = false;
+    }
+    const double halfmin = 0.5 * std::min({box.prd[0], box.prd[1], box.prd[2]});
+    dev->bond_minimg = (all_fene && 2.0 * r0max * 1.000001 < halfmin && !rebuild_knobs.freeze_images) ? 1 : 0;
+  }
+  dev->newton_pair = newton_pair ? 1 : 0;
+  for (int k = 0; k < 3; k++) {
+    const double binsize_optimal = cutneighmax > 0.0 ? 0.5 * cutneighmax : box.prd[0];
+    int nb = (int)(box.prd[k] * (1.0 / binsize_optimal));
+    if (nb == 0) nb = 1;
+    dev->ref_nbin[k] = nb;
+    dev->ref_bininv[k] = 1.0 / (box.prd[k] / nb);
+  }
+  le_reneigh_step.assign(fixes.size(), -1);
+  dev->le_snapshot = 0;
+  for (auto &f : fixes) if (f->force_reneighbor) dev->le_snapshot = 1;
+  note_topology_changed(*dev);     // bond tables may have been edited between runs
+  dev_edits_at_run = dev_edits;    // (the setup rebuild refreshes every ghost)
+  halo_step = -1;
+  host_current = false;
 }
 
 }  // namespace lmp_le

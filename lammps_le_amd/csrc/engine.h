@@ -289,6 +289,7 @@ struct ThermoRow {
   double eangle = 0.0;                 // sum over the listed angles
   double ptensor[6] = {0, 0, 0, 0, 0, 0};   // pxx pyy pzz pxy pxz pyz (src/compute_pressure.cpp:244-290), when asked for
   bool has_ptensor = false;
+  double fmax = 0.0, fnorm = 0.0;      // max |f_ic| and sqrt(f.f) (src/thermo.cpp compute_fmax / compute_fnorm), when asked for
 };
 
 class Engine {
@@ -407,7 +408,31 @@ class Engine {
   void respa_level_forces(int ilevel);
   void compute_forces(bool eflag);
   ThermoRow eval_thermo(bool ke_summed = false);
+  // the row from the sums of one evaluation: s = the sixteen of the force kernel, then rows of 16 per wall and per force fix;
+  // a8 = the angles' (null: none), k6 = the kinetic tensor (null: not asked for)
+  ThermoRow thermo_from_sums(const double *s, const double *a8, const double *k6);
+  std::string thermo_float_format;     // thermo_modify format float: a checked printf conversion ("": %12.8g)
+  bool want_fnorm = false;            // fmax or fnorm was named: thermo steps also reduce the force norms
   void print_thermo_header();
+  // what `run` and `minimize` do between init() and their setup: upload or refresh of the device state, the tables of the
+  // walls and force fixes, the modes of this run
+  void begin_run_state();
+  // ---- minimize (minimize.cpp; src/minimize.cpp, min.cpp, min_linesearch.cpp, min_cg.cpp, min_sd.cpp) ----
+  std::string min_style = "cg";        // (src/update.cpp:60-62: cg without the command)
+  double min_dmax = 0.1;               // min_modify (src/min.cpp:50-80 defaults)
+  int min_linestyle = 1;               // 0 backtrack, 1 quadratic
+  int min_normstyle = 0;               // 0 two, 1 max, 2 inf
+  std::map<std::string, std::string> min_other;   // the keywords of fire / spin: stored, without effect on cg and sd
+  void min_style_command(std::vector<std::string> &arg);
+  void min_modify_command(std::vector<std::string> &arg);
+  void minimize(double etol, double ftol, long maxiter, long maxeval);
+  // of the last minimisation (lammps_le_stat min_*): iterations, evaluations, index into the stop strings, the last line
+  // search's alpha, host waits, list builds, and the energies of the stats block
+  long min_niter = 0, min_neval = 0, min_host_waits = 0, min_rebuilds = 0;
+  int min_stop = 0;
+  double min_alpha = 0.0, min_einitial = 0.0, min_eprevious = 0.0, min_efinal = 0.0;
+  double min_fnorm2_init = 0.0, min_fnorminf_init = 0.0, min_fnorm2_final = 0.0, min_fnorminf_final = 0.0;
+  static const char *min_stop_string(int n);
   // one thermo keyword (src/thermo.cpp:1572-2110 compute_*): false when the keyword is unknown.  `r` = the row the energies
   // come from; `isint` = printed with the integer format (BIGINT fields)
   bool thermo_keyword(const ThermoRow &r, const std::string &k, double &val, bool &isint);
@@ -548,6 +573,7 @@ class Engine {
   std::map<std::string, std::vector<double>> restart_origins;            // fix ID -> origins of a fix spring/self in the file
   void apply_restart_state(Fix *f);
   bool dump_due(long step) const;
+  bool dump_force_all = false;       // the last iteration of a minimisation that stopped early: every dump is due (src/min.cpp:446-449)
   void write_dumps(long step);       // downloads, then writes every dump that is due
   void build_special();               // src/special.cpp:55-
   void create_box_atoms_check();

@@ -661,7 +661,25 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
         else if (arg[i + 1] == "multi") thermo_multi = true;
         else throw LammpsError("Illegal thermo_modify command");
       }
-      else if (arg[i] == "format") { i += 3; continue; }
+      else if (arg[i] == "format") {
+        // `format float FMT` (src/thermo.cpp:600-640): one printf conversion for every floating-point column; the other
+        // forms (line, int, a column index) are accepted and keep the default
+        if (arg[i + 1] == "none") { thermo_float_format.clear(); i += 2; continue; }
+        if (i + 3 > arg.size()) throw LammpsError("Illegal thermo_modify command");
+        if (arg[i + 1] == "float") {
+          const std::string &f = arg[i + 2];
+          size_t p = 0;
+          bool ok = !f.empty() && f[p++] == '%';
+          while (ok && p < f.size() && strchr("-+ 0#", f[p])) p++;
+          while (ok && p < f.size() && isdigit((unsigned char)f[p])) p++;
+          if (ok && p < f.size() && f[p] == '.') { p++; while (p < f.size() && isdigit((unsigned char)f[p])) p++; }
+          ok = ok && p + 1 == f.size() && strchr("eEfFgG", f[p]) && f.size() < 16;
+          if (!ok) throw LammpsError("MI355X engine: thermo_modify format float takes one %e, %f or %g conversion");
+          thermo_float_format = f;
+        }
+        i += 3;
+        continue;
+      }
       i += 2;
     }
   } else if (cmd == "timestep") {
@@ -680,6 +698,14 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
       else throw LammpsError("MI355X engine: run keyword " + arg[k] + " is not supported");
     }
     run(nrun);
+  } else if (cmd == "minimize") {            // src/minimize.cpp:31-47
+    if (arg.size() != 4) throw LammpsError("Illegal minimize command");
+    if (!box_exist) throw LammpsError("Minimize command before simulation box is defined");
+    minimize(numeric(arg[0]), numeric(arg[1]), (long)inumeric(arg[2]), (long)inumeric(arg[3]));
+  } else if (cmd == "min_style") {
+    min_style_command(arg);
+  } else if (cmd == "min_modify") {
+    min_modify_command(arg);
   } else if (cmd == "write_data") {
     need(1);
     write_data(arg[0]);
@@ -1862,7 +1888,7 @@ void Engine::init_local_compute(const LocalCompute &c) const {
 // atom-ID order, which is the reference's order at 1 rank with `atom_modify sort 0 0` (or `dump_modify sort id`).
 // ---------------------------------------------------------------------------------------------
 bool Engine::dump_due(long step) const {
-  for (auto &dp : dumps) if (step % dp.every == 0 && dp.last != step) return true;
+  for (auto &dp : dumps) if ((step % dp.every == 0 || dump_force_all) && dp.last != step) return true;
   return false;
 }
 void Engine::write_dumps(long step) {
@@ -1874,7 +1900,7 @@ void Engine::write_dumps(long step) {
   // any compute column lists the bonds, as a dump of bond columns does)
   bool need_host = false;
   for (auto &dp : dumps) {
-    if (step % dp.every != 0 || dp.last == step) continue;
+    if ((step % dp.every != 0 && !dump_force_all) || dp.last == step) continue;
     int pair_cols = 0, bond_cols = 0;
     if (dp.style == "local")
       for (auto &a : dp.cols) if (a != "index") (col_kind(a) == LOCAL_BOND ? bond_cols : pair_cols)++;
@@ -1884,7 +1910,7 @@ void Engine::write_dumps(long step) {
   if (need_host) download();  // collective when decomposed; every rank then holds the whole system
   host_current = false;
   for (auto &dp : dumps) {
-    if (step % dp.every != 0 || dp.last == step) continue;
+    if ((step % dp.every != 0 && !dump_force_all) || dp.last == step) continue;
     dp.last = step;
     auto member = [&](int i, int bit) { return bit == 1 || (!gmask.empty() && (gmask[i] & bit)); };
     long nrows = 0;

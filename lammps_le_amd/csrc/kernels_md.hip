@@ -1758,6 +1758,28 @@ void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *ou
   for (int k = 0; k < 16 * ft.n; k++) out[k] = d.partial_h[k];
 }
 
+// every sum of a thermo evaluation added up where it lies: the same k_colsum launches as the reduce_* functions above, no copy
+void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, bool angles, MinSources &src) {
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  const size_t rows = (size_t)d.nred_blocks + 1;
+  hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, (d.n + BLOCK - 1) / BLOCK, d.partial, d.partial + (size_t)((d.n + BLOCK - 1) / BLOCK) * 16);
+  src.add(d.partial + (size_t)((d.n + BLOCK - 1) / BLOCK) * 16, 16);
+  if (angles) {
+    hipLaunchKernelGGL((k_colsum<8>), dim3(1), dim3(BLOCK), 0, d.stream, nb, d.partial_a, d.partial_a + (size_t)nb * 8);
+    src.add(d.partial_a + (size_t)nb * 8, 8);
+  }
+  for (int k = 0; k < wt.n; k++) {
+    double *tab = d.wall_partial + (size_t)k * rows * 16;
+    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+    src.add(tab + (size_t)nb * 16, 16);
+  }
+  for (int k = 0; k < ft.n; k++) {
+    double *tab = d.forceop_partial + (size_t)k * rows * 16;
+    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+    src.add(tab + (size_t)nb * 16, 16);
+  }
+}
+
 // sum the per-block partials in a fixed order (deterministic); the totals land in the table's spare row nb
 void reduce_partials(DeviceState &d, double *out16) {
   int nb = (d.n + BLOCK - 1) / BLOCK;
