@@ -11,6 +11,7 @@
 #include "comm.h"
 #include "device.h"
 #include "soft_inl.h"
+#include "indent_inl.h"
 
 namespace lmp_le { unsigned dd_halo_mismatches(DeviceState &d); }
 using namespace lmp_le;
@@ -157,8 +158,9 @@ void *lammps_extract_fix(void *handle, char *id, int style, int type, int nrow, 
   BEGIN_CAPTURE
     Fix *f = e->find_fix(id);
     if (!f) throw LammpsError(std::string("Could not find fix ID ") + id);
-    // (the fixes with a global scalar: wall/region, spring/self, addforce)
-    const bool scalar = style == 0 && type == 0 && (dynamic_cast<FixWallRegion *>(f) || dynamic_cast<FixSpringSelf *>(f) || dynamic_cast<FixAddForce *>(f));
+    // (the fixes with a global scalar: wall/region, spring/self, addforce, indent)
+    const bool scalar = style == 0 && type == 0 && (dynamic_cast<FixWallRegion *>(f) || dynamic_cast<FixSpringSelf *>(f) || dynamic_cast<FixAddForce *>(f) ||
+                                                    dynamic_cast<FixIndent *>(f));
     if (!scalar && (style != 0 || type != 1)) throw LammpsError("MI355X engine: only global fix vectors can be extracted");
     if (!scalar && f->size_vector() >= 0 && (nrow < 0 || nrow >= f->size_vector()))
       throw LammpsError("MI355X engine: fix vector is accessed out-of-range");
@@ -651,7 +653,7 @@ static const std::vector<std::pair<std::string, std::vector<std::string>>> &styl
       {"bond", {"fene", "harmonic", "hybrid", "none", "zero"}},
       {"compute", {"pair/local", "property/local"}},
       {"dump", {"atom", "custom", "dcd", "local"}},
-      {"fix", {"adapt", "addforce", "bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "langevin", "nve", "setforce", "spring/self", "wall/region"}},
+      {"fix", {"adapt", "addforce", "bond/break", "bond/create", "ex_load", "ex_unload", "extrusion", "indent", "langevin", "nve", "setforce", "spring/self", "wall/region"}},
       {"pair", {"lj/cut", "none", "soft", "zero"}},
   };
   return t;
@@ -829,6 +831,7 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "steps_unfused") return (double)e->steps_unfused;
   if (k == "steps_fused_ext") return (double)e->steps_fused_ext;        // of steps_fused: spring/self, addforce, setforce inside the step kernel
   if (k == "steps_fused_wall") return (double)e->steps_fused_wall;      // of steps_fused: fix wall/region inside the step kernel
+  if (k == "steps_fused_indent") return (double)e->steps_fused_indent;  // of steps_fused: the launch carried an indenter of fix indent
   if (k == "steps_fused_soft") return (double)e->steps_fused_soft;      // of steps_fused: pair_style soft inside the step kernel
   if (k == "pair_table_copies") return (double)e->pair_table_copies;    // fix adapt: copies of the pair table in the middle of runs
   // the last `minimize`: iterations, force evaluations, index into Min::stopstrings, the last line search's alpha, times the host
@@ -933,6 +936,49 @@ extern "C" void lammps_le_test_soft_pair(int n, const double *rsq, double a, dou
     fpair[i] = lmp_le::soft_pair<true>(rsq[i], seed, a_pi_rc, pi_rc, a, e);
     evdwl[i] = e;
   }
+}
+
+// test hook (not part of the reference surface, not declared in include/lammps_le.h):
+// indent_force (indent_inl.h) compiled for the host: n beads (x[3n]) against one indenter on the orthogonal box lo / hi.
+// geo = kind, axis, side | planeside, K, ctr x y z (as written: remapped here by indent_remap, as FixIndent::entry does), R | pos;
+// f[3n] the force on every bead, sums[4] the columns in bead order
+extern "C" void lammps_le_test_indent_force(int n, const double *x, const double *lo, const double *hi, const double *geo, double *f,
+                                            double *sums) {
+  Box box{};
+  for (int c = 0; c < 3; c++) { box.lo[c] = lo[c]; box.hi[c] = hi[c]; box.prd[c] = hi[c] - lo[c]; box.half[c] = 0.5 * box.prd[c]; box.iprd[c] = 1.0 / box.prd[c]; }
+  IndentEntry o{};
+  o.kind = (int)geo[0]; o.axis = (int)geo[1]; o.side = (int)geo[2]; o.groupbit = 1;
+  o.k = geo[3]; o.k3 = o.k / 3.0; o.r = geo[7];
+  for (int c = 0; c < 3; c++)
+    o.ctr[c] = indent_remap((o.kind == INDENT_CYLINDER && c == o.axis) ? box.lo[c] : geo[4 + c], box.lo[c], box.hi[c], box.prd[c]);
+  for (int c = 0; c < 4; c++) sums[c] = 0.0;
+  for (int i = 0; i < n; i++) {
+    double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+    indent_force<true>(x[3 * i], x[3 * i + 1], x[3 * i + 2], o, box, f0, f1, f2, sums);
+    f[3 * i] = f0; f[3 * i + 1] = f1; f[3 * i + 2] = f2;
+  }
+}
+
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): the table of fix indent that the force
+// evaluation of step `now` of a run over steps [begin, end] would carry, without a device - the init() of a run command, the
+// fixes in order, the formulas evaluated, the centres remapped.  out: per indenter ten numbers - kind, axis, side | planeside,
+// group bit, phase, K, centre x y z, radius | position.  Returns the number of indenters, or -1 with the error recorded
+extern "C" int lammps_le_test_indent_table(void *handle, long begin, long end, long now, double *out) {
+  BEGIN_CAPTURE
+  struct InRun { Engine *e; bool was; long b0, e0, n0; InRun(Engine *en) : e(en), was(en->in_run), b0(en->beginstep), e0(en->endstep), n0(en->ntimestep) {}
+                 ~InRun() { e->in_run = was; e->beginstep = b0; e->endstep = e0; e->ntimestep = n0; } } keep(e);
+  e->init();
+  e->build_indent_list();
+  e->in_run = true; e->beginstep = begin; e->endstep = end; e->ntimestep = now;
+  const IndentTable t = e->indent_table();
+  for (int k = 0; k < t.n; k++) {
+    const IndentEntry &o = t.e[k];
+    const double row[10] = {(double)o.kind, (double)o.axis, (double)o.side, (double)o.groupbit, (double)o.phase, o.k, o.ctr[0], o.ctr[1], o.ctr[2], o.r};
+    for (int c = 0; c < 10; c++) out[10 * k + c] = row[c];
+  }
+  return t.n;
+  END_CAPTURE
+  return -1;
 }
 
 // test hook (not part of the reference surface, not declared in include/lammps_le.h): the derived pair coefficients as the

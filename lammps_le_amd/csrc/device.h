@@ -307,6 +307,8 @@ struct DeviceState {
   int *lgrank = nullptr;                                // [maxtag+2] rank of a bead among the members of fix langevin's group (local order)
   WallTable *walltab_dev = nullptr;                     // fix wall/region: this run's table (k_wall, the wall variant of k_step)
   double *wall_partial = nullptr;                       // [WALL_MAX][nred_blocks + 1][16] block sums of k_wall<EFLAG> + their totals
+  double *indent_partial = nullptr;                     // [INDENT_MAX][nred_blocks + 1][16] block sums of k_indent<EFLAG> + their totals
+  int indent_count = 0;                                 // fix indent instances of this run : what a fused launch must carry
   // fix spring/self | addforce | setforce: this run's table (k_fixforce, the EXT variant of k_step); one block of unwrapped
   // origins per spring/self fix, [3][ntotal + 1] by tag, never permuted, whole on every rank of a decomposed run
   ForceOpTable *forceoptab_dev = nullptr;
@@ -388,7 +390,7 @@ struct DeviceState {
 // minimize: the columns of a dots pass (the first MIN_NSUM are sums, the others maxima), the record's capacity and the
 // totals of other reductions that travel with it (each `len` doubles in device memory, appended behind the dots)
 enum MinDotCol { MIN_FF = 0, MIN_FH = 1, MIN_FG = 2, MIN_FMAX2 = 3, MIN_FMAXC = 4, MIN_HMAXC = 5 };
-constexpr int MIN_NSUM = 3, MIN_DOT_USED = 6, MIN_DOT_COLS = 8, MIN_REC_MAX = 256, MIN_SRC_MAX = 16;
+constexpr int MIN_NSUM = 3, MIN_DOT_USED = 6, MIN_DOT_COLS = 8, MIN_REC_MAX = 256, MIN_SRC_MAX = 20;
 struct MinSources {
   int n = 0;
   const double *ptr[MIN_SRC_MAX] = {nullptr};
@@ -427,6 +429,7 @@ struct StepArgs {
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // sampled launches: the kernel's own begin / end timestamps
   bool swap_buffers = true;                           // a `next` launch leaves the new positions in d.pos
   unsigned ext_active = 0;                            // EXT: bit k - entry k of the force-op table acts on this step (addforce `every`)
+  const IndentTable *indents = nullptr;               // INDENT: the indenters of the step whose forces the launch computes (copied into the launch)
 };
 void launch_step(DeviceState &d, const StepPlan &plan, const StepArgs &args);
 void launch_langevin(DeviceState &d, const TypeTables &tt, bool identity_rank, bool fuse_final, int groupbit = 1);
@@ -448,6 +451,12 @@ void reduce_angle_partials(DeviceState &d, double *out8);
 void upload_wall_table(DeviceState &d, const WallTable &wt);
 void launch_wall(DeviceState &d, const WallTable &wt, int phase, bool eflag);
 void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out);
+// fix indent (kernels_md.hip): the rows of block sums of a run; the indenters of one place among the post-force fixes added to f -
+// the table goes by value with the launch (eflag: with the four block sums per indenter); those sums on the host, rows of 16
+// per indenter (synchronises the stream)
+void reserve_indent_partials(DeviceState &d);
+void launch_indent(DeviceState &d, const IndentTable &it, int phase, bool eflag);
+void reduce_indent_partials(DeviceState &d, int nindent, double *out);
 // fix spring/self | addforce | setforce (kernels_md.hip): the table of a run with the origin blocks (`origins[k]`: the host
 // block [natoms][3] of entry k, null for an entry that has none; the table's entries get the device addresses); the entries of
 // one phase applied to f in table order (`active`: bit k - entry k acts on this step; eflag: with the ten block sums per
@@ -460,7 +469,7 @@ void reduce_partials(DeviceState &d, double *out16);
 
 // the same sums left in device memory without a copy or a wait (the totals land in the spare row of each table): where they
 // are, for a record that collects them (kernels_min.hip k_min_collect)
-void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, bool angles, MinSources &src);
+void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, int nindent, bool angles, MinSources &src);
 
 // minimize (kernels_min.hip).  min_alloc: the partials and the record, with `vectors` also x0 g h; min_free releases the
 // vectors and, with `all`, the rest.

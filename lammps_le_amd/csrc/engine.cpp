@@ -928,7 +928,48 @@ void Engine::build_wall_table() {
 }
 void Engine::wall_post_force(int phase, bool eflag) {
   if (walltab.n) launch_wall(*dev, walltab, phase, eflag);
+  // fix indent behind the walls of its place: the geometry of this force evaluation, once for both places
+  if (!indent_fixes.empty()) {
+    if (phase == 0) indent_now = indent_table();
+    launch_indent(*dev, indent_now, phase, eflag);
+  }
   forceop_post_force(phase, eflag);      // within a phase the walls act first (build_forceop_table holds the scripts to that)
+}
+
+// fix indent: the fixes of this run in fix order, each with its place relative to fix langevin (as the walls)
+void Engine::build_indent_list() {
+  indent_fixes.clear();
+  indent_phase.clear();
+  indent_now = IndentTable{};
+  int phase = 0;
+  for (auto &f : fixes) {
+    if (dynamic_cast<FixLangevin *>(f.get())) phase = 1;
+    auto *o = dynamic_cast<FixIndent *>(f.get());
+    if (!o) continue;
+    if ((int)indent_fixes.size() >= INDENT_MAX) throw LammpsError("internal: more than INDENT_MAX fix indent instances");
+    indent_fixes.push_back(o);
+    indent_phase.push_back(phase);
+  }
+}
+// The table of one force evaluation: FixIndent::post_force's head for every indenter - the formulas with ntimestep as it stands,
+// the centre remapped - evaluated on the host between two launches
+IndentTable Engine::indent_table() {
+  IndentTable t{};
+  for (size_t k = 0; k < indent_fixes.size(); k++) {
+    IndentEntry e = indent_fixes[k]->entry();
+    e.phase = indent_phase[k];
+    t.e[t.n++] = e;
+  }
+  return t;
+}
+static int indents_request(const Engine *e) {      // StepRequest::indents
+  if (e->indent_fixes.empty()) return 0;
+  for (auto *o : e->indent_fixes) if (o->groupbit != 1) return 2;
+  return 1;
+}
+static bool indents_behind_langevin(const Engine *e) {
+  for (int ph : e->indent_phase) if (ph) return true;
+  return false;
 }
 
 // fix spring/self | addforce | setforce: the table of this run, in fix order (the order the reference runs post_force in, which
@@ -946,6 +987,9 @@ void Engine::build_forceop_table() {
     if (dynamic_cast<FixWallRegion *>(f.get()) && order_matters[phase])
       throw LammpsError("MI355X engine: fix " + f->id + " (wall/region) is defined behind a fix addforce or setforce on the same side of "
                         "fix langevin; define the wall first");
+    if (dynamic_cast<FixIndent *>(f.get()) && order_matters[phase])
+      throw LammpsError("MI355X engine: fix " + f->id + " (indent) is defined behind a fix addforce or setforce on the same side of "
+                        "fix langevin; define the indenter first");
     auto *o = dynamic_cast<FixForceOp *>(f.get());
     if (!o) continue;
     if (forceoptab.n >= FORCEOP_MAX) throw LammpsError("internal: more than FORCEOP_MAX force fixes");
@@ -1051,12 +1095,14 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
   if (!ke_summed) launch_ke(d, tt);       // (the energy variant of the step kernel has summed the kinetic energy as well)
   // behind the sixteen sums of the force kernel: the ten of every wall (rows of 16), in the same all-reduce
   // ... and behind those the ten of every spring/self, addforce and setforce
-  double s[16 + 16 * WALL_MAX + 16 * FORCEOP_MAX];
+  // ... and behind those the four of every indenter
+  double s[16 + 16 * WALL_MAX + 16 * FORCEOP_MAX + 16 * INDENT_MAX];
   reduce_partials(d, s);
-  const int nwall = walltab.n, nops = forceoptab.n;
+  const int nwall = walltab.n, nops = forceoptab.n, nind = (int)indent_fixes.size();
   if (nwall) reduce_wall_partials(d, walltab, s + 16);
   if (nops) reduce_fixforce_partials(d, forceoptab, s + 16 + 16 * nwall);
-  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * (nwall + nops));
+  if (nind) reduce_indent_partials(d, nind, s + 16 + 16 * (nwall + nops));
+  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * (nwall + nops + nind));
   double a8[8], k6[6];
   const bool ang = angles_active();
   if (ang) {
@@ -1109,6 +1155,11 @@ ThermoRow Engine::thermo_from_sums(const double *s, const double *a8, const doub
     for (int c = 0; c < FORCEOP_COLS; c++) if (c < 4 || acted) o->sums[c] = s[16 + 16 * (nwall + k) + c];
     if (o->thermo_energy) efix += o->compute_scalar();
     if (o->thermo_virial) for (int c = 0; c < 6; c++) vfix[c] += o->sums[4 + c];
+  }
+  for (size_t k = 0; k < indent_fixes.size(); k++) {      // FixIndent::compute_scalar / compute_vector; no virial (virial_flag 0)
+    FixIndent *o = indent_fixes[k];
+    for (int c = 0; c < INDENT_COLS; c++) o->indenter[c] = s[16 + 16 * (nwall + nops + (int)k) + c];
+    if (o->thermo_energy) efix += o->indenter[0];
   }
   ThermoRow r{};
   r.step = ntimestep;
@@ -1265,7 +1316,7 @@ void Engine::setup() {
   double s1 = wall();
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = steps_fused_indent = 0;
   adapt_apply(true);                              // FixAdapt::setup_pre_force
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
@@ -1311,6 +1362,7 @@ void Engine::iterate(long nsteps) {
   rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_force(); rq.soft = pair_soft; rq.angles = ang;
   rq.nvebit = fusable ? nbits[0] : 1; rq.lgbit = lg ? lg->groupbit : 1;
   rq.walls = walls_request(this);
+  rq.indents = indents_request(this);
   rq.ext = forceoptab.n > 0;
   bool pre_integrated = false;
   const bool adapting = have_adapt();
@@ -1342,6 +1394,11 @@ void Engine::iterate(long nsteps) {
     StepArgs sa;
     sa.bt = &bondtab; sa.special_lj = special_lj; sa.tt = &tt; sa.dtv = dt; sa.triggersq = triggersq;
     sa.ext_active = forceop_active();      // (of the step whose forces the launch computes: this one, not its NEXT half's)
+    // fix indent: the geometry of this step - evaluated here, between two launches, and carried by the launch itself.  (The
+    // plan is taken again behind the rebuild with `check` and `cells` set; whether it is fused with the wall flag depends on
+    // neither, so this answer holds for the launch)
+    const bool indents_fused = plan.fused && plan.indent;
+    if (indents_fused) { indent_now = indent_table(); sa.indents = &indent_now; }
     stamp();
     if (!pre_integrated) {
       bool will_check = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
@@ -1411,7 +1468,8 @@ void Engine::iterate(long nsteps) {
       pre_integrated = next;
       steps_fused++;
       if (plan.grp) steps_fused_group++;
-      if (plan.wall) steps_fused_wall++;
+      if (plan.wall && walltab.n) steps_fused_wall++;
+      if (plan.indent) steps_fused_indent++;
       if (plan.soft) steps_fused_soft++;
       if (plan.ext) steps_fused_ext++;
       stamp(T_PAIR);          // the fused kernel: pair + bond + post_force + final_integrate (+ next initial_integrate)
@@ -1440,7 +1498,7 @@ void Engine::iterate(long nsteps) {
       // fix wall/region at its place among the post-force fixes: before fix langevin, or behind it (no fused half-kick then)
       wall_post_force(0, eflag || ext_sums);
       const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag &&
-                                  !walls_behind_langevin(this) && !forceops_behind_langevin(this);
+                                  !walls_behind_langevin(this) && !forceops_behind_langevin(this) && !indents_behind_langevin(this);
       if (lg) langevin_post_force(this, lg, lg_fused_final);
       wall_post_force(1, eflag || ext_sums);
       if (!lg_fused_final)
@@ -1489,7 +1547,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = 0;
+  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = steps_fused_indent = 0;
   for (int l = 0; l <= top; l++) {
     if (l == top) adapt_apply(true);           // FixAdapt::setup_pre_force_respa: the outermost level only
     respa_level_forces(l);
@@ -1497,7 +1555,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   }
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
-  if (lg || walltab.n || forceoptab.n) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
+  if (lg || walltab.n || forceoptab.n || !indent_fixes.empty()) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
     launch_flevel_copy(d, d.respa_flevel[top], false, false);     // FixWallRegion::setup likewise (ilevel_respa = the outermost)
     wall_post_force(0, true);
     if (lg) langevin_post_force(this, lg, false);
@@ -1709,7 +1767,12 @@ void Engine::begin_run_state() {
   build_wall_table();
   // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
   //  region ends every rank - the error flag travels with the displacement test's reduction, Engine::decide)
-  if (walltab.n) upload_wall_table(*dev, walltab);
+  // fix indent: its fixes in order; their table travels with the launches, the rows of block sums are reserved here.  The wall
+  // variant of the step kernel reads the wall table whenever it runs: a run with indenters alone gets one with n = 0
+  build_indent_list();
+  dev->indent_count = (int)indent_fixes.size();
+  if (walltab.n || !indent_fixes.empty()) upload_wall_table(*dev, walltab);
+  if (!indent_fixes.empty()) reserve_indent_partials(*dev);
   // fix spring/self | addforce | setforce: the table (built above) and the origin blocks of the tethers (by tag, whole on every rank)
   if (forceoptab.n) {
     std::vector<const double *> origins;

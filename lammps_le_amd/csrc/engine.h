@@ -41,6 +41,7 @@ constexpr int NN_SHIFTED_BIT = 1 << 30;
 constexpr int BSHIFT_BITS = 6;
 constexpr int FORCEOP_MAX = 8;    // fix spring/self | addforce | setforce instances one run can hold (ForceOpTable)
 constexpr int WALL_MAX = 4;        // fix wall/region instances one run can hold (WallTable)
+constexpr int INDENT_MAX = 4;      // fix indent instances one run can hold (IndentTable)
 
 // ---------------------------------------------------------------------------------------------
 // RanMars in exact integer arithmetic (src/random_mars.cpp:29-95; every value is k * 2^-24)
@@ -105,6 +106,27 @@ struct WallTable {
   int n;
   WallEntry w[WALL_MAX];
 };
+
+// fix indent (src/fix_indent.cpp): what the kernels need of every indenter.  Filled on the host for every force evaluation - the
+// geometry may be a formula of the step - and handed to the kernels by value, so a moving indenter costs no copy and no wait
+enum IndentKind { INDENT_SPHERE = 0, INDENT_CYLINDER = 1, INDENT_PLANE = 2 };
+struct IndentEntry {
+  int kind;                   // IndentKind
+  int axis;                   // cylinder: its axis; plane: its normal (0 x, 1 y, 2 z)
+  int side;                   // sphere | cylinder: side in (1) | out (0); plane: planeside, lo (-1) | hi (+1)
+  int groupbit;               // the fix's group (1 = all)
+  int phase;                  // 0: before fix langevin or without one, 1: behind it
+  int pad;
+  double k, k3;               // K and K / 3
+  double ctr[3];              // sphere | cylinder: the centre, remapped into the box as Domain::remap does
+  double r;                   // sphere | cylinder: the radius; plane: its position
+};
+struct IndentTable {
+  int n;
+  int pad;
+  IndentEntry e[INDENT_MAX];
+};
+constexpr int INDENT_COLS = 4;     // sums per entry: energy, force on the indenter x y z
 
 // fix spring/self | addforce | setforce (src/fix_spring_self.cpp, fix_addforce.cpp, fix_setforce.cpp): the post-force fixes that
 // act on chosen beads from outside, in the order the fixes were defined; built on the host at every `run`
@@ -237,6 +259,26 @@ struct FixWallRegion : Fix {
   double compute_vector(int n) override { return ewall[n + 1]; }
   int size_vector() const override { return 3; }
   bool extensive() const override { return true; }       // (src/fix_wall_region.cpp:45-46)
+};
+
+// fix ID group indent K <sphere x y z R | cylinder dim c1 c2 R | plane dim pos lo|hi> [side in|out] [units box|lattice]
+// (src/fix_indent.cpp).  The force lives in indent_inl.h (indent_force); this object holds the script's numbers and variable
+// names and the sums of the last evaluation with sums
+struct FixIndent : Fix {
+  int istyle = INDENT_SPHERE, cdim = 0, side = 0, planeside = 0;
+  double k = 0.0, k3 = 0.0;
+  double value[5] = {0, 0, 0, 0, 0};                     // x y z R pos as numbers
+  std::string vstr[5];                                   // ... or as the name of an equal-style variable ("": a number)
+  bool thermo_energy = false;                            // fix_modify energy (THERMO_ENERGY; the fix has no virial)
+  double indenter[4] = {0, 0, 0, 0};                     // energy and the force on the indenter
+  FixIndent(Engine *e, const std::vector<std::string> &arg);
+  void init() override;                                  // FixIndent::init: the variables exist and are equal-style, host-evaluable
+  bool varflag() const { for (auto &v : vstr) if (!v.empty()) return true; return false; }
+  IndentEntry entry();                                   // the geometry of step Engine::ntimestep (FixIndent::post_force's head)
+  double compute_scalar() override { return indenter[0]; }
+  double compute_vector(int n) override { return indenter[n + 1]; }
+  int size_vector() const override { return 3; }
+  bool extensive() const override { return true; }       // (src/fix_indent.cpp:51-52)
 };
 
 // fix ID group spring/self K [dir] | addforce fx fy fz [every N] | setforce fx|NULL fy|NULL fz|NULL.  The force lives in
@@ -373,7 +415,8 @@ class Engine {
   long pair_table_copies = 0;       // mid-run copies of the pair table by fix adapt (lammps_le_stat "pair_table_copies")
   std::string pair_sig;             // pair style and neighbor cutoff of the last upload
   bool in_run = false;              // Update::whichflag != 0: ramp() is legal
-  std::string host_only_for;        // != "": a formula evaluated for this fix adapt variable must not read the device
+  std::string host_only_for;        // != "": a formula evaluated for this variable of a fix must not read the device
+  std::string host_only_style = "adapt";   // ... the style of that fix (adapt | indent), for the message (HostOnlyScope sets both)
   void adapt_apply(bool setup);     // FixAdapt::setup_pre_force / pre_force of every fix adapt, then Pair::reinit + push
   void adapt_post_run();            // FixAdapt::post_run: reset yes
   bool adapt_set_values(bool setup);   // the host part of adapt_apply: true when a coefficient was set (and all derived again)
@@ -408,7 +451,7 @@ class Engine {
   void respa_level_forces(int ilevel);
   void compute_forces(bool eflag);
   ThermoRow eval_thermo(bool ke_summed = false);
-  // the row from the sums of one evaluation: s = the sixteen of the force kernel, then rows of 16 per wall and per force fix;
+  // the row from the sums of one evaluation: s = the sixteen of the force kernel, then rows of 16 per wall, per force fix and per indenter;
   // a8 = the angles' (null: none), k6 = the kinetic tensor (null: not asked for)
   ThermoRow thermo_from_sums(const double *s, const double *a8, const double *k6);
   std::string thermo_float_format;     // thermo_modify format float: a checked printf conversion ("": %12.8g)
@@ -456,7 +499,14 @@ class Engine {
   WallTable walltab{};
   std::vector<FixWallRegion *> wall_fixes;
   void build_wall_table();            // at every run (init() has checked the regions); emptied when the set of fixes changes
-  void wall_post_force(int phase, bool eflag);   // k_wall for the walls before (0) / behind (1) fix langevin
+  void wall_post_force(int phase, bool eflag);   // k_wall, k_indent, k_fixforce for the fixes before (0) / behind (1) fix langevin
+  // fix indent: the fixes of this run (fix order) and their place relative to fix langevin; the table of one force evaluation
+  std::vector<FixIndent *> indent_fixes;
+  std::vector<int> indent_phase;
+  long steps_fused_indent = 0;        // of steps_fused: the launch carried an indenter (lammps_le_stat "steps_fused_indent")
+  void build_indent_list();           // at every run, beside build_wall_table()
+  IndentTable indent_table();         // the geometry of step `ntimestep`: formulas evaluated on the host, centres remapped
+  IndentTable indent_now{};           // ... of the force evaluation under way
   // fix spring/self | addforce | setforce: the table of this run (fix order), the fixes behind its rows
   ForceOpTable forceoptab{};
   std::vector<FixForceOp *> forceop_fixes;
@@ -649,5 +699,18 @@ double numeric(const std::string &s);
 int inumeric(const std::string &s);
 std::vector<std::string> split_words(const std::string &line);
 void bounds(const std::string &s, int nmax, int &lo, int &hi);   // "*", "n*", "*m", "n*m" type ranges (src/utils.cpp bounds)
+
+// While it lives, formulas are evaluated for variable `var` of a fix of style `style` and may read nothing that lives on the
+// device (Parser, input.cpp); what was set before comes back when it goes, also on an exception
+struct HostOnlyScope {
+  Engine *e;
+  std::string was_for, was_style;
+  HostOnlyScope(Engine *en, const std::string &var, const std::string &style) : e(en), was_for(en->host_only_for), was_style(en->host_only_style) {
+    e->host_only_for = var; e->host_only_style = style;
+  }
+  ~HostOnlyScope() { e->host_only_for = was_for; e->host_only_style = was_style; }
+  HostOnlyScope(const HostOnlyScope &) = delete;
+  HostOnlyScope &operator=(const HostOnlyScope &) = delete;
+};
 
 }  // namespace lmp_le

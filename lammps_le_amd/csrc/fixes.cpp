@@ -6,6 +6,7 @@
 
 #include "comm.h"
 #include "device.h"
+#include "indent_inl.h"
 
 namespace lmp_le {
 
@@ -251,6 +252,107 @@ void FixAdapt::init() {
                  ~Dry() { e->in_run = was; e->host_only_for.clear(); } } dry(eng, c.var);
     (void)eng->variable_value(c.var);
   }
+}
+
+// fix ID group indent K <sphere x y z R | cylinder dim c1 c2 R | plane dim pos lo|hi> [side in|out] [units box|lattice]
+// (src/fix_indent.cpp:41-91, options :405-528): the keywords in any order, each geometric value a number or v_name.  There is no
+// lattice command here, so both `units` values scale by 1 (as `region` treats them)
+FixIndent::FixIndent(Engine *e, const std::vector<std::string> &arg) {
+  eng = e; id = arg[0]; group = arg[1]; style = arg[2];
+  const char *ill = "Illegal fix indent command";
+  if (arg.size() < 4) throw LammpsError(ill);
+  groupbit = fix_group(e, arg);
+  k = numeric(arg[3]);
+  k3 = k / 3.0;
+  bool have = false;
+  auto read = [&](const std::string &w, int slot) {
+    if (w.rfind("v_", 0) == 0) vstr[slot] = w.substr(2);
+    else value[slot] = numeric(w);
+  };
+  size_t i = 4;
+  const size_t n = arg.size();
+  while (i < n) {
+    if (arg[i] == "sphere") {
+      if (i + 5 > n) throw LammpsError(ill);
+      for (int c = 0; c < 4; c++) read(arg[i + 1 + c], c);
+      istyle = INDENT_SPHERE; have = true;
+      i += 5;
+    } else if (arg[i] == "cylinder") {
+      if (i + 5 > n) throw LammpsError(ill);
+      if (arg[i + 1] == "x") { cdim = 0; read(arg[i + 2], 1); read(arg[i + 3], 2); }
+      else if (arg[i + 1] == "y") { cdim = 1; read(arg[i + 2], 0); read(arg[i + 3], 2); }
+      else if (arg[i + 1] == "z") { cdim = 2; read(arg[i + 2], 0); read(arg[i + 3], 1); }
+      else throw LammpsError(ill);
+      read(arg[i + 4], 3);
+      istyle = INDENT_CYLINDER; have = true;
+      i += 5;
+    } else if (arg[i] == "plane") {
+      if (i + 4 > n) throw LammpsError(ill);
+      if (arg[i + 1] == "x") cdim = 0;
+      else if (arg[i + 1] == "y") cdim = 1;
+      else if (arg[i + 1] == "z") cdim = 2;
+      else throw LammpsError(ill);
+      read(arg[i + 2], 4);
+      if (arg[i + 3] == "lo") planeside = -1;
+      else if (arg[i + 3] == "hi") planeside = 1;
+      else throw LammpsError(ill);
+      istyle = INDENT_PLANE; have = true;
+      i += 4;
+    } else if (arg[i] == "units") {
+      if (i + 2 > n || (arg[i + 1] != "box" && arg[i + 1] != "lattice")) throw LammpsError(ill);
+      i += 2;
+    } else if (arg[i] == "side") {
+      if (i + 2 > n) throw LammpsError(ill);
+      if (arg[i + 1] == "in") side = 1;
+      else if (arg[i + 1] == "out") side = 0;
+      else throw LammpsError(ill);
+      i += 2;
+    } else throw LammpsError(ill);
+  }
+  if (!have) throw LammpsError(ill);
+  has_post_force = true;
+}
+// FixIndent::init (:118-160): the variables exist and are equal-style (the x variable's text differs, as in the reference).  A
+// formula is evaluated on the host between two launches of a run: one that reads what lives on the device is refused here, at
+// the run command, with the name of what it reads (Parser, input.cpp)
+void FixIndent::init() {
+  for (int c = 0; c < 5; c++) {
+    if (vstr[c].empty()) continue;
+    if (eng->variables.find(vstr[c]) == eng->variables.end()) throw LammpsError("Variable name for fix indent does not exist");
+    auto vi = eng->var_info.find(vstr[c]);
+    if (vi == eng->var_info.end() || vi->second.style != "equal")
+      throw LammpsError(c == 0 ? "Variable for fix indent is invalid style" : "Variable for fix indent is not equal style");
+    struct Dry { Engine *e; bool was; Dry(Engine *en) : e(en), was(en->in_run) { e->in_run = true; } ~Dry() { e->in_run = was; } } dry(eng);
+    HostOnlyScope scope(eng, vstr[c], "indent");
+    (void)eng->variable_value(vstr[c]);
+  }
+}
+// FixIndent::post_force's head (:196-212, :250-280, :332-334): the values of this step, the centre through Domain::remap (the
+// box is periodic in every dimension: while below lo add a period, while at or above hi take one off, then max(coord, lo))
+IndentEntry FixIndent::entry() {
+  double v[5];
+  for (int c = 0; c < 5; c++) {
+    v[c] = value[c];
+    if (vstr[c].empty()) continue;
+    HostOnlyScope scope(eng, vstr[c], "indent");
+    v[c] = eng->variable_value(vstr[c]);
+  }
+  IndentEntry e{};
+  e.kind = istyle; e.axis = cdim; e.groupbit = groupbit;
+  e.k = k; e.k3 = k3;
+  if (istyle == INDENT_PLANE) {
+    e.side = planeside;
+    e.r = v[4];
+    return e;
+  }
+  e.side = side;
+  e.r = v[3];
+  const Box &b = eng->box;
+  for (int c = 0; c < 3; c++) {
+    const double x = (istyle == INDENT_CYLINDER && c == cdim) ? b.lo[c] : v[c];      // (the axis coordinate is not used: "just near box")
+    e.ctr[c] = indent_remap(x, b.lo[c], b.hi[c], b.prd[c]);
+  }
+  return e;
 }
 
 // fix ID group wall/region region-ID style args cutoff  (src/fix_wall_region.cpp:35-92): lj93 | lj126 | lj1043 | harmonic take

@@ -52,7 +52,7 @@ std::vector<std::string> split_words(const std::string &line) {
 
 // ---------------------------------------------------------------------------------------------
 // formulas (src/variable.cpp Variable::evaluate, the subset a bead-spring script uses): numbers, + - * / % ^, unary -,
-// comparisons and && || !, parentheses, sqrt exp ln log abs sin cos tan floor ceil round min max ramp, thermo keywords
+// comparisons and && || !, parentheses, sqrt exp ln log abs sin cos tan floor ceil round min max ramp vdisplace, thermo keywords
 // (step dt atoms bonds vol temp press pe ke etotal epair emol), v_name, f_ID[k]
 // ---------------------------------------------------------------------------------------------
 namespace {
@@ -108,7 +108,7 @@ struct Parser {
     if (name.rfind("v_", 0) == 0) return e->variable_value(name.substr(2));
     if (name.rfind("f_", 0) == 0) {
       if (!e->host_only_for.empty())
-        throw LammpsError("MI355X engine: variable " + e->host_only_for + " of fix adapt reads " + name +
+        throw LammpsError("MI355X engine: variable " + e->host_only_for + " of fix " + e->host_only_style + " reads " + name +
                           ", which lives on the device (numbers, step, elapsed, dt, time, ramp() and the math functions are evaluated per step)");
       int idx = 1;
       bool indexed = false;
@@ -126,6 +126,13 @@ struct Parser {
       double a = expr(), b = 0.0;
       bool two = eat(",");
       if (two) b = expr();
+      // (swiggle, cwiggle: the reference's three-argument functions, which this parser does not have - named as unknown
+      //  functions; a third argument to anything else is the syntax error it always was)
+      if (two && (name == "swiggle" || name == "cwiggle") && eat(",")) {
+        (void)expr();
+        if (!eat(")")) bad();
+        throw LammpsError("Invalid math function in variable formula: " + name);
+      }
       if (!eat(")")) bad();
       if (name == "sqrt") { if (a < 0.0) throw LammpsError("Sqrt of negative value in variable formula"); return sqrt(a); }
       if (name == "exp") return exp(a);
@@ -146,6 +153,11 @@ struct Parser {
         if (delta != 0.0) delta /= (double)(e->endstep - e->beginstep);
         return a + delta * (b - a);
       }
+      if (name == "vdisplace" && two) {   // src/variable.cpp:3743-3754
+        if (!e->in_run) throw LammpsError("Cannot use vdisplace in variable formula between runs");
+        const double delta = (double)(e->ntimestep - e->beginstep);
+        return a + b * delta * e->dt;
+      }
       throw LammpsError("Invalid math function in variable formula: " + name);
     }
     if (name == "step") return (double)e->ntimestep;
@@ -161,7 +173,7 @@ struct Parser {
         e->thermo_keyword(e->last_thermo, name, val, isint);
         return val;
       }
-      throw LammpsError("MI355X engine: variable " + e->host_only_for + " of fix adapt reads " + name +
+      throw LammpsError("MI355X engine: variable " + e->host_only_for + " of fix " + e->host_only_style + " reads " + name +
                         ", which lives on the device (numbers, step, elapsed, dt, time, ramp() and the math functions are evaluated per step)");
     }
     {
@@ -584,6 +596,13 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
       if (walls >= WALL_MAX)
         throw LammpsError("MI355X engine: at most " + std::to_string(WALL_MAX) + " fix wall/region instances (WALL_MAX in engine.h)");
     }
+    else if (st == "indent") {
+      int indents = 0;
+      for (auto &g : fixes) if (dynamic_cast<FixIndent *>(g.get())) indents++;
+      f.reset(new FixIndent(this, arg));
+      if (indents >= INDENT_MAX)
+        throw LammpsError("MI355X engine: at most " + std::to_string(INDENT_MAX) + " fix indent instances (INDENT_MAX in engine.h)");
+    }
     else if (st == "spring/self" || st == "addforce" || st == "setforce") {
       int ops = 0;
       for (auto &g : fixes) if (dynamic_cast<FixForceOp *>(g.get())) ops++;
@@ -599,6 +618,7 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     fixes.push_back(std::move(f));
     walltab.n = 0; wall_fixes.clear();      // (the next run builds the table of its walls)
     forceoptab.n = 0; forceop_fixes.clear();
+    indent_fixes.clear(); indent_phase.clear();
   } else if (cmd == "unfix") {
     need(1);
     auto it = std::find_if(fixes.begin(), fixes.end(), [&](const std::unique_ptr<Fix> &f) { return f->id == arg[0]; });
@@ -606,6 +626,7 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     fixes.erase(it);
     walltab.n = 0; wall_fixes.clear();
     forceoptab.n = 0; forceop_fixes.clear();
+    indent_fixes.clear(); indent_phase.clear();
   } else if (cmd == "fix_modify") {
     // src/modify.cpp:1052-1066 modify_fix, src/fix.cpp:134-176 modify_params: energy / virial for a fix that has them
     if (arg.size() < 2) throw LammpsError("Illegal fix_modify command");
@@ -613,6 +634,7 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     if (!f) throw LammpsError("Could not find fix_modify ID");
     auto *w = dynamic_cast<FixWallRegion *>(f);
     auto *o = dynamic_cast<FixForceOp *>(f);
+    auto *ind = dynamic_cast<FixIndent *>(f);
     for (size_t k = 1; k < arg.size(); k += 2) {
       if (k + 2 > arg.size()) throw LammpsError("Illegal fix_modify command");
       const std::string &kw = arg[k], &val = arg[k + 1];
@@ -622,10 +644,15 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
         //  capability, src/fix.cpp:146-163)
         if (o && (val == "no" || (kw == "energy" ? o->has_energy : o->has_virial))) (kw == "energy" ? o->thermo_energy : o->thermo_virial) = val == "yes";
         else if (o) throw LammpsError("Illegal fix_modify command");
+        // (fix indent has THERMO_ENERGY and no virial_flag: `virial yes` is illegal, src/fix.cpp:155-162)
+        else if (ind && (kw == "energy" || val == "no")) { if (kw == "energy") ind->thermo_energy = val == "yes"; }
+        else if (ind) throw LammpsError("Illegal fix_modify command");
         else if (!w) throw LammpsError("Illegal fix_modify command");      // (no other fix here has THERMO_ENERGY / virial_flag)
         else (kw == "energy" ? w->thermo_energy : w->thermo_virial) = val == "yes";
       } else if (kw == "respa" && w) {
         throw LammpsError("MI355X engine: fix_modify respa is not supported (fix wall/region acts at the outermost level)");
+      } else if (kw == "respa" && ind) {
+        throw LammpsError("MI355X engine: fix_modify respa is not supported (fix indent acts at the outermost level)");
       } else if (kw == "respa" && o) {
         throw LammpsError("MI355X engine: fix_modify respa is not supported (fix " + o->style +
                           (o->kind == FORCEOP_SET ? " is refused under run_style respa)" : " acts at the outermost level)"));

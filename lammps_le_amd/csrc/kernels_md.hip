@@ -16,6 +16,7 @@
 #include "device.h"
 #include "bin_inl.h"
 #include "soft_inl.h"
+#include "indent_inl.h"
 #include <hip/hip_ext.h>
 #include <cstring>
 
@@ -252,6 +253,9 @@ struct StepKernelArgs {
   const ForceOpTable *ext;
   const int *img;
   unsigned ext_active;
+  // INDENT (behind everything else, as above): the indenters of fix indent with the geometry of the step whose forces this launch
+  // computes - by value, so a radius that is a formula of the step costs no copy on the stream and no wait (n = 0: none)
+  IndentTable indents;
 };
 
 // reciprocal by v_rcp_f64 + two Newton steps (<= 1 ulp from the IEEE quotient 1/x; an IEEE divide is ~35 instructions)
@@ -732,6 +736,52 @@ __global__ __launch_bounds__(BLOCK) void k_wall(int n, const double4 *__restrict
   if (live) { fx[p] = f0; fy[p] = f1; fz[p] = f2; }
 }
 
+// fix indent (indent_inl.h): the indenters of one place among the post-force fixes on a bead of group all, in table order -
+// what the indent variants of the step kernel run behind that place's walls.  The table is a kernel argument: n, the phases and
+// the kinds are the same for every lane
+__device__ __forceinline__ void indents_on_bead(const IndentTable &it, int phase, const double4 &x, const Box &box, double &f0,
+                                                double &f1, double &f2) {
+  const int ni = it.n;
+#pragma unroll 1
+  for (int k = 0; k < ni; k++) {
+    const IndentEntry &o = it.e[k];
+    if (o.phase != phase) continue;
+    indent_force<false>(x.x, x.y, x.z, o, box, f0, f1, f2, nullptr);
+  }
+}
+// the unfused post-force kernel of fix indent: the indenters of one `phase` added to f for the members of each fix's group;
+// EFLAG: per indenter the block sums of the four columns of indent_force into rows of 16 (k_colsum<16> adds them up)
+template <bool EFLAG>
+__global__ __launch_bounds__(BLOCK) void k_indent(int n, const double4 *__restrict__ pos, const int *__restrict__ tag,
+                                                  const int *__restrict__ gmask, IndentTable it, Box box, int phase,
+                                                  double *__restrict__ fx, double *__restrict__ fy, double *__restrict__ fz,
+                                                  double *__restrict__ partial, int rows) {
+  const int p = blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = p < n;
+  double4 x = make_double4(0.0, 0.0, 0.0, 0.0);
+  double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+  int gm = 1;
+  if (live) {
+    x = pos[p];
+    f0 = fx[p]; f1 = fy[p]; f2 = fz[p];
+    if (gmask) gm = gmask[tag[p]] | 1;
+  }
+  const int ni = it.n;
+  for (int k = 0; k < ni; k++) {
+    const IndentEntry &o = it.e[k];
+    if (o.phase != phase) continue;
+    double acc[INDENT_COLS];
+#pragma unroll
+    for (int c = 0; c < INDENT_COLS; c++) acc[c] = 0.0;
+    if (live && (gm & o.groupbit)) indent_force<EFLAG>(x.x, x.y, x.z, o, box, f0, f1, f2, acc);
+    if (EFLAG) {
+      block_reduce_store<INDENT_COLS>(acc, partial + (size_t)k * rows * 16, blockIdx.x, 0);
+      __syncthreads();       // (the next indenter reuses the reduction's LDS)
+    }
+  }
+  if (live) { fx[p] = f0; fy[p] = f1; fz[p] = f2; }
+}
+
 // ------------------------------------------------------------------------------------------
 // fix spring/self | addforce | setforce: the entries [k0, k1) of the run's table that belong to `phase` (0 before fix langevin or
 // without one, 1 behind it) and act on this step (`active`, bit k) applied to one bead, in table = fix order - setforce overwrites
@@ -932,12 +982,14 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // WALL: fix wall/region on group all (wall_force): the walls defined before fix langevin add their force before drag and noise,
 // the ones behind it after - the order the reference's post_force hooks run in; the wall needs nothing but the bead's own
 // position, which is in registers here (four lanes per bead: lane 0, behind the butterfly)
+// INDENT: fix indent on group all (indent_force) on top of WALL, behind the walls of each place; a run with indenters alone
+// carries a wall table with n = 0.  A flag of its own: sharing WALL's made wall-only runs 3.7 % slower (fix indent)
 // EXT: fix spring/self, addforce, setforce (forceops_on_bead) at their place among the post-force fixes, as the walls; the bead's
 // group bits come by tag (not loaded when every entry is on group all), its images and origin only if it is a member
 // The parameters from `tag` on are the members of S and k_step's five direct pointers once more, __restrict__-qualified: the
 // loads of level 0 / level 1 below and of the AHEAD shapes move ahead of the stores into `flags` only with it (StepKernelArgs).
 // Read straight from S here, the members give 2 instantiations other VGPR counts and the wall variants vector loads of their table.
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL, bool SOFT, bool EXT>
+template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL, bool SOFT, bool EXT, bool INDENT>
 __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt, const StepKernelArgs &S,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
@@ -951,7 +1003,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
                                           const int *__restrict__ gmask, int nvebit, int lgbit,
                                           const int *__restrict__ vperm, double *__restrict__ vxo,
                                           double *__restrict__ vyo, double *__restrict__ vzo,
-                                          const WallTable *__restrict__ wt) {
+                                          const WallTable *__restrict__ wt, const IndentTable &indents) {
   int lb = logical_block(A.nblocks);
   const int sub = (LPB == 1) ? 0 : (int)(threadIdx.x % LPB);
   int p = lb * (BLOCK / LPB) + threadIdx.x / LPB;
@@ -1002,6 +1054,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   // (a bead outside its region raises the error flag here, ahead of the `poisoned` test below: a launch that is discarded and
   //  repeated after a list overflow reports it one launch early, from the same positions the repeated launch reads)
   if (WALL) walls_on_bead(wt, 0, ri, f0, f1, f2, flags);
+  if (INDENT) indents_on_bead(indents, 0, ri, box, f0, f1, f2);
   if (EXT) forceops_on_bead<false>(S.ext, 0, S.ext->n, 0, S.ext_active, ri, gm_ext, t, S.img, A.npad, p, box, f0, f1, f2, nullptr);
   if (LANGEVIN && (!GRP || m_lg)) {
     double gamma1 = tt.g1[type], gamma2 = tt.g2[type];
@@ -1016,6 +1069,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
     f2 += fdrag2 + fran2;
   }
   if (WALL && LANGEVIN) walls_on_bead(wt, 1, ri, f0, f1, f2, flags);
+  if (INDENT && LANGEVIN) indents_on_bead(indents, 1, ri, box, f0, f1, f2);
   if (EXT && LANGEVIN) forceops_on_bead<false>(S.ext, 0, S.ext->n, 1, S.ext_active, ri, gm_ext, t, S.img, A.npad, p, box, f0, f1, f2, nullptr);
   if (poisoned) return;
   const double dtfm = tt.dtfm[type];
@@ -1077,7 +1131,7 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   else { vx[p] = a; vy[p] = b; vz[p] = c; }
 }
 template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
-          bool GRP = false, bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false>
+          bool GRP = false, bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false>
 __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
                                                                                            StepKernelArgs S, double *__restrict__ fx,
                                                                                            double *__restrict__ fy, double *__restrict__ fz,
@@ -1092,6 +1146,7 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
                 "soft variant: the three plain shapes with a pair style");
   static_assert(!EXT || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && !SOFT && (LPB == 1 || AHEAD)),
                 "EXT variant: the three plain shapes with a pair style");
+  static_assert(!INDENT || (WALL && !SOFT && !EXT), "indent variant: a wall variant that also takes the launch's indenters");
   static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
                 "velocity hand-over: the throughput shape only");
   static_assert(!EF || (!NEXT && LPB == 1), "energy variant: NEXT = false, one lane per bead");
@@ -1108,9 +1163,9 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT, EXT>(
+  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT, EXT, INDENT>(
       A, bt, box, tt, S, s_tab, s_bt, S.tag, S.ranks, S.draws, S.vx, S.vy, S.vz, fx, fy, fz, pos_next, xhold, S.dtv, S.triggersq, S.check, S.flags,
-      S.phase, S.which, e, kev[0], S.gmask, S.nvebit, S.lgbit, S.vperm, S.vxo, S.vyo, S.vzo, S.walls);
+      S.phase, S.which, e, kev[0], S.gmask, S.nvebit, S.lgbit, S.vperm, S.vxo, S.vyo, S.vzo, S.walls, S.indents);
   if (EF) {
     const int lb = logical_block(A.nblocks);
     if (lb < A.nblocks) {
@@ -1307,6 +1362,18 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
 template <class F>
 static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
+  if (p.indent) {
+    // the indent variants are wall variants with one more flag: enumerated on their own, as the EXT variants below
+    if (!p.wall || !p.pair || p.diag || p.ang || p.ef || p.grp || lazy_v || p.soft || p.ext) return false;
+    with_flags([&](auto L, auto N, auto I, auto W4, auto H) {
+      constexpr int W = W4 ? 4 : 1;
+      if constexpr (step_variant_exists(L, N, I, true, W, false, H, false, false, false, false, true, false, false, true)) {
+        f(k_step<L, N, I, true, W, false, H, false, false, false, false, true, false, false, true>);
+        found = true;
+      }
+    }, p.langevin, p.next, p.ident, p.lpb == 4, p.ahead);
+    return found;
+  }
   if (p.ext) {
     // the EXT variants differ in five flags only; a fourteenth flag in the enumeration below would double what the host
     // compiler has to expand (2^13 -> 2^14 bodies)
@@ -1332,6 +1399,7 @@ static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
 static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArgs &A, const StepArgs &a, hipEvent_t ev_start,
                                hipEvent_t ev_stop) {
   StepKernelArgs S = {};
+  IndentTable itab{};
   S.tag = d.tag; S.draws = d.rng_out;
   // fixes on groups (GRP): the draws of a thermostat on a group go by the rank among its members
   S.ranks = p.member_ranks ? d.lgrank : d.crank;
@@ -1348,6 +1416,11 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
     if (!d.walltab_dev) throw LammpsError("internal: fused wall step without the wall table");
     S.walls = d.walltab_dev;
   }
+  // fix indent: a run with indenters takes the indent variants, and the launch carries the table of every one of them
+  // (DeviceState::indent_count) - a launch without it would drop them silently
+  if (p.fused && (p.indent != (d.indent_count > 0) || (p.indent && (!a.indents || a.indents->n != d.indent_count))))
+    throw LammpsError("internal: fused step without the table of this run's indenters");
+  if (p.indent) itab = *a.indents;
   if (p.ext) {
     if (!d.forceoptab_dev) throw LammpsError("internal: fused EXT step without the force-op table");
     if (d.forceop_grouped && !d.gmask) throw LammpsError("internal: fused EXT step on groups without group masks");
@@ -1366,6 +1439,7 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
   const bool lazy_v = d.v_pending && takes_pending_v(p, d.dd != 0);
   if (!lazy_v) settle_velocities(d);
   const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel) {
+    S.indents = itab;
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, S,
                           d.f[0], d.f[1], d.f[2], d.pos_tmp, d.xhold);
   });
@@ -1417,10 +1491,10 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
 // ... grp), bin, member_ranks, diag_bits, lds_pad, whether the dispatcher of launch_step holds the instantiation the plan names
 // (its own look-up, nothing is launched), then [16] = StepPlan::wall and [17] = the plan takes velocities a rebuild left pending
 static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out, int soft = 0, int *out_soft = nullptr,
-                           int ext = 0, int *out_ext = nullptr) {
+                           int ext = 0, int *out_ext = nullptr, int indents = 0, int *out_indent = nullptr) {
   StepRequest r;
   r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
-  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0; r.ext = ext != 0;
+  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0; r.ext = ext != 0; r.indents = indents;
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
   const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
   const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
@@ -1428,6 +1502,7 @@ static void test_step_plan(int n_owned, int decomposed, const int *req, int wall
   for (int k = 0; k < 18; k++) out[k] = v[k];
   if (out_soft) *out_soft = p.soft;
   if (out_ext) *out_ext = p.ext;
+  if (out_indent) *out_indent = p.indent;
 }
 // eleven inputs (no walls), the first 16 outputs
 extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
@@ -1449,6 +1524,13 @@ extern "C" void lammps_le_test_step_plan_soft(int n_owned, int decomposed, const
 extern "C" void lammps_le_test_step_plan_ext(int n_owned, int decomposed, const int *req, int *out) {
   test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19);
   out[20] = count_step_variants();
+}
+// fifteen inputs, req[14] = indenters (StepRequest::indents); the 21 outputs of the hook above, then [21] = StepPlan::indent and
+// [22] = count_all_step_variants(), the number of instantiations with the indent variants
+extern "C" void lammps_le_test_step_plan_indent(int n_owned, int decomposed, const int *req, int *out) {
+  test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19, req[14], out + 21);
+  out[20] = count_step_variants();
+  out[22] = count_all_step_variants();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1697,6 +1779,38 @@ void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out) {
   for (int k = 0; k < 16 * wt.n; k++) out[k] = d.partial_h[k];
 }
 
+// fix indent: the rows of block sums (the table itself travels with every launch)
+void reserve_indent_partials(DeviceState &d) {
+  const size_t np = (size_t)INDENT_MAX * (d.nred_blocks + 1) * 16;
+  DEV_RESERVE(d.mem, d.indent_partial, np);
+  HIP_CHECK(hipMemsetAsync(d.indent_partial, 0, np * sizeof(double), d.stream));
+}
+void launch_indent(DeviceState &d, const IndentTable &it, int phase, bool eflag) {
+  bool any = false, grouped = false;
+  if (it.n < 0 || it.n > INDENT_MAX) throw LammpsError("internal: fix indent table with a bad count");
+  for (int k = 0; k < it.n; k++) if (it.e[k].phase == phase) { any = true; grouped = grouped || it.e[k].groupbit != 1; }
+  if (!any) return;
+  if (!d.indent_partial) throw LammpsError("internal: fix indent without its rows of block sums");
+  if (grouped && !d.gmask) throw LammpsError("internal: fix indent on a group without group masks");
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  if (nb > d.nred_blocks) throw LammpsError("internal: more blocks than rows of block sums");
+  with_flags([&](auto E) {
+    hipLaunchKernelGGL((k_indent<E>), dim3(nb), dim3(BLOCK), 0, d.stream, d.n, d.pos, d.tag, grouped ? d.gmask : (const int *)nullptr,
+                       it, d.box, phase, d.f[0], d.f[1], d.f[2], d.indent_partial, d.nred_blocks + 1);
+  }, eflag);
+}
+void reduce_indent_partials(DeviceState &d, int nindent, double *out) {
+  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
+  const size_t rows = (size_t)d.nred_blocks + 1;
+  for (int k = 0; k < nindent; k++) {
+    double *tab = d.indent_partial + (size_t)k * rows * 16;
+    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+    HIP_CHECK(hipMemcpyAsync(d.partial_h + 16 * (size_t)k, tab + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
+  }
+  stream_sync(d);
+  for (int k = 0; k < 16 * nindent; k++) out[k] = d.partial_h[k];
+}
+
 void upload_forceop_table(DeviceState &d, ForceOpTable &ft, const double *const *origins, int natoms) {
   const size_t stride = (size_t)natoms + 1;
   ft.stride = (int)stride;
@@ -1759,7 +1873,7 @@ void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *ou
 }
 
 // every sum of a thermo evaluation added up where it lies: the same k_colsum launches as the reduce_* functions above, no copy
-void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, bool angles, MinSources &src) {
+void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, int nindent, bool angles, MinSources &src) {
   const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
   const size_t rows = (size_t)d.nred_blocks + 1;
   hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, (d.n + BLOCK - 1) / BLOCK, d.partial, d.partial + (size_t)((d.n + BLOCK - 1) / BLOCK) * 16);
@@ -1777,6 +1891,11 @@ void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable
     double *tab = d.forceop_partial + (size_t)k * rows * 16;
     hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
     src.add(tab + (size_t)nb * 16, 16);
+  }
+  for (int k = 0; k < nindent; k++) {      // (the four columns of an indenter)
+    double *tab = d.indent_partial + (size_t)k * rows * 16;
+    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+    src.add(tab + (size_t)nb * 16, INDENT_COLS);
   }
 }
 

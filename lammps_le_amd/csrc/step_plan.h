@@ -31,12 +31,14 @@ struct StepKnobs {
 // angle style is active; thermo: thermo output after this step, energies and virial are wanted; check: the displacement test
 // of Neighbor::check_distance is due; cells: the cell tables the binning writes are allocated; walls: fix wall/region - 0 none,
 // 1 walls the step kernel can take (every one on group all), 2 walls that force the unfused kernels (one of them on a group);
-// soft: the pair style is soft, not lj/cut (pair is set as well); ext: fix spring/self, addforce or setforce act (on any group)
+// soft: the pair style is soft, not lj/cut (pair is set as well); ext: fix spring/self, addforce or setforce act (on any group);
+// indents: fix indent, coded as walls - 0 none, 1 every one on group all, 2 one of them on a group
 struct StepRequest {
   bool langevin = false, next = false, ident = false, pair = false, angles = false, thermo = false, check = false, cells = false;
   int nvebit = 1, lgbit = 1; // group bits of fix nve / fix langevin (1 = all)
   int which = -1;            // decomposed runs with halo / compute overlap: the phase this launch handles (-1: every bead)
   int walls = 0;
+  int indents = 0;
   bool soft = false;
   bool ext = false;
 };
@@ -47,7 +49,8 @@ struct StepPlan {
   bool langevin = false, next = false, ident = false, pair = false;
   int lpb = 1;
   bool diag = false, ahead = false, ang = false, ef = false, grp = false;
-  bool wall = false;         // fix wall/region evaluated inside the kernel (wall_force)
+  bool wall = false;         // fix wall/region evaluated inside the kernel (wall_force); also set with `indent`
+  bool indent = false;       // fix indent evaluated inside the kernel (indent_force): the wall variant with the launch's indenters
   bool soft = false;         // pair_style soft: the soft functor of pair_term
   bool ext = false;          // fix spring/self | addforce | setforce evaluated inside the kernel (forceops_on_bead)
   bool bin = false;          // positions binned by this launch
@@ -68,23 +71,26 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   p.langevin = r.langevin; p.next = r.next; p.ident = r.ident; p.pair = r.pair;
   p.which = r.which; p.nvebit = r.nvebit; p.lgbit = r.lgbit; p.check = r.check; p.lds_pad = k.lds_pad;
   p.grp = r.nvebit != 1 || r.lgbit != 1;
-  if (r.walls) {
-    // fix wall/region: the wall variant covers the plain steps of a run whose walls all act on group all, with a pair style, no
-    // angle style and no fix on a group; thermo steps (the wall's energy and virial) and everything else take k_wall
-    if (r.walls != 1 || p.grp || r.thermo || r.angles || !r.pair) return unfused;
+  const bool confined = r.walls || r.indents;
+  if (confined) {
+    // fix wall/region, fix indent: the wall variant covers the plain steps of a run whose walls and indenters all act on group
+    // all, with a pair style, no angle style and no fix on a group; thermo steps (the fixes' sums) and everything else take
+    // k_wall and k_indent
+    if (r.walls == 2 || r.indents == 2 || p.grp || r.thermo || r.angles || !r.pair) return unfused;
     p.wall = true;
+    p.indent = r.indents != 0;      // (a run with indenters alone carries a wall table with n = 0)
   }
   if (r.soft) {
     // pair_style soft: the soft variant covers what the wall variant covers - plain steps, no angle style, no fix on a group -
     // and not together with walls; thermo steps and everything else take k_force<.., SOFT>
-    if (!r.pair || r.walls || p.grp || r.thermo || r.angles) return unfused;
+    if (!r.pair || confined || p.grp || r.thermo || r.angles) return unfused;
     p.soft = true;
   }
   if (r.ext) {
     // fix spring/self | addforce | setforce: the EXT variant covers what the wall variant covers - plain steps with a pair style,
     // no angle style, no fix nve / langevin on a group - and not together with walls or pair_style soft; the fixes' own groups
     // are tested inside the kernel.  Thermo steps (the fixes' sums) and everything else take k_fixforce
-    if (!r.pair || r.walls || r.soft || p.grp || r.thermo || r.angles) return unfused;
+    if (!r.pair || confined || r.soft || p.grp || r.thermo || r.angles) return unfused;
     p.ext = true;
   }
   if (p.grp) {
@@ -113,13 +119,14 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   return p;
 }
 
-// The instantiations of k_step that exist, by its fourteen template arguments (what plan_step plans with; implies the six
+// The instantiations of k_step that exist, by its template arguments (what plan_step plans with; implies the
 // static_asserts inside k_step): 24 + 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 153
 constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
-                                   bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false) {
+                                   bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false) {
+  if (INDENT) return WALL && P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !SOFT && !EXT && (LPB == 1 || AHEAD);   // fix indent inside the wall variant: L, N, I x three shapes = 24
   if (EXT) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && !SOFT && (LPB == 1 || AHEAD);   // spring/self, addforce, setforce inside the step: L, N, I x three shapes = 24
   if (SOFT) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && (LPB == 1 || AHEAD);   // pair_style soft inside the step: L, N, I x three shapes = 24
-  if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region inside the step: L, N, I x three shapes = 24
+  if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region | indent inside the step: L, N, I x three shapes = 24
   if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
   if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
   if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
@@ -134,12 +141,21 @@ constexpr int count_step_variants() {
   return c;
 }
 static_assert(count_step_variants() == 153, "the set of k_step instantiations changed");
+// ... and with the fifteenth argument, INDENT (fix indent has a flag of its own, so that a wall variant without indenters is
+// the code it was): 153 + 24 = 177
+constexpr int count_all_step_variants() {
+  int c = count_step_variants();
+  for (int m = 0; m < 16384; m++)
+    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048, m & 4096, m & 8192, true);
+  return c;
+}
+static_assert(count_all_step_variants() == 177, "the set of k_step instantiations changed");
 
 // The launch of this plan takes the velocities a rebuild left in the old order (DeviceState::v_pending): the throughput shape
 // of the kernel, in one launch over every bead of one GPU, with no diagnostic launch in front of it.  Engine::iterate asks
 // before it lets a rebuild leave them, launch_step when it picks the instantiation.
 inline bool takes_pending_v(const StepPlan &p, bool decomposed) {
-  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall, p.soft, p.ext) &&
+  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall, p.soft, p.ext, p.indent) &&
          p.which < 0 && !p.diag_bits && !decomposed;
 }
 
