@@ -1110,3 +1110,42 @@ extern "C" void lammps_le_debug_le_array(void *handle, int slot, int n, int *out
   if (out_i) (void)hipMemcpy(out_i, e->dev->le_i[slot], (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
   if (out_d) (void)hipMemcpy(out_d, e->dev->le_d[0], (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
 }
+
+// test hooks of the launch census (not part of the reference surface, not declared in include/lammps_le.h).  kernel: 0 = k_step
+// (keys: step_variant_key), 1 = k_force (force_variant_key), step_plan.h.
+// The launches of a handle so far as (key, count) pairs with count > 0, ascending by key; returns how many there are (at most
+// `cap` are stored)
+extern "C" int lammps_le_test_step_census(void *handle, int kernel, int cap, int *keys, long long *counts) {
+  lmp_le::Engine *e = (lmp_le::Engine *)handle;
+  if (!e || !e->dev) return 0;
+  const unsigned *c = kernel ? e->dev->force_census : e->dev->step_census;
+  const int space = kernel ? lmp_le::FORCE_KEY_SPACE : lmp_le::STEP_KEY_SPACE;
+  int n = 0;
+  for (int k = 0; k < space; k++)
+    if (c[k]) { if (n < cap) { keys[n] = k; counts[n] = c[k]; } n++; }
+  return n;
+}
+extern "C" void lammps_le_test_step_census_reset(void *handle) {
+  lmp_le::Engine *e = (lmp_le::Engine *)handle;
+  if (!e || !e->dev) return;
+  std::fill(e->dev->step_census, e->dev->step_census + lmp_le::STEP_KEY_SPACE, 0u);
+  std::fill(e->dev->force_census, e->dev->force_census + lmp_le::FORCE_KEY_SPACE, 0u);
+}
+// the keys of the instantiations that exist (step_variant_exists; the condition of launch_force), ascending, without a device;
+// returns how many there are
+extern "C" int lammps_le_test_step_keys(int kernel, int cap, int *keys) {
+  const int space = kernel ? lmp_le::FORCE_KEY_SPACE : lmp_le::STEP_KEY_SPACE;
+  int n = 0;
+  for (int k = 0; k < space; k++)
+    if (kernel ? lmp_le::force_key_exists(k) : lmp_le::step_key_exists(k)) { if (n < cap) keys[n] = k; n++; }
+  return n;
+}
+// key -> the template arguments in the template's order (k_step: fifteen, LPB as 1 | 4; k_force: four) and back
+extern "C" void lammps_le_test_step_key_decode(int kernel, int key, int *flags) {
+  if (kernel) for (int b = 0; b < lmp_le::FORCE_KEY_BITS; b++) flags[b] = (key >> b) & 1;
+  else lmp_le::step_key_decode(key, flags);
+}
+extern "C" int lammps_le_test_step_key(int kernel, const int *f) {
+  if (kernel) return lmp_le::force_variant_key(f[0], f[1], f[2], f[3]);
+  return lmp_le::step_variant_key(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14]);
+}

@@ -44,9 +44,24 @@ Engine::Engine(int argc, char **argv) {
   thermo_keywords = {"step", "temp", "epair", "emol", "etotal", "press"};
   const char *kt = getenv("LAMMPS_LE_KERNEL_TIMING");
   kernel_timing = kt && atoi(kt) != 0;
+  if (const char *cf = getenv("LAMMPS_LE_STEP_CENSUS_FILE")) census_file = cf;
+}
+
+// LAMMPS_LE_STEP_CENSUS_FILE: "step <key> <launches>" / "force <key> <launches>" per instantiation this handle launched, in
+// one write (several processes may append to the one file)
+static void append_census(const std::string &path, const DeviceState &d) {
+  std::string out;
+  char buf[64];
+  for (int k = 0; k < STEP_KEY_SPACE; k++)
+    if (d.step_census[k]) { snprintf(buf, sizeof buf, "step %d %u\n", k, d.step_census[k]); out += buf; }
+  for (int k = 0; k < FORCE_KEY_SPACE; k++)
+    if (d.force_census[k]) { snprintf(buf, sizeof buf, "force %d %u\n", k, d.force_census[k]); out += buf; }
+  if (out.empty()) return;
+  if (FILE *fp = fopen(path.c_str(), "a")) { fwrite(out.data(), 1, out.size(), fp); fclose(fp); }
 }
 
 Engine::~Engine() {
+  if (dev && !census_file.empty()) append_census(census_file, *dev);
   if (dev) {
     try { dev_free(*dev); } catch (...) {}
     delete dev;      // (its registry lets go of what dev_free keeps: comm_stream, its events, the timing events)

@@ -530,6 +530,7 @@ class Engine {
   void stamp();                // Timer::stamp()      : restart the section clock
   void stamp(int which);       // Timer::stamp(which) : add the time since the previous stamp to a section
   void print_timing_breakdown(long nsteps);   // src/finish.cpp:318-370
+  std::string census_file;     // LAMMPS_LE_STEP_CENSUS_FILE=path (read once, here): ~Engine appends this handle's launch census to it
   bool kernel_timing = false;  // LAMMPS_LE_KERNEL_TIMING=1: HIP events around sampled step-kernel launches
   double kstat_ms = 0.0;       // mean step-kernel duration of the last run (ms)
   long kstat_n = 0;

@@ -1354,11 +1354,14 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
   }
   if (parts == 1) A.diag = 1;      // pairs only (bonds only: straight from the bond-partner table)
   with_flags([&](auto E, auto P, auto NOBOND, auto SOFT) {
-    if constexpr ((P || !NOBOND) && (P || !SOFT))
+    if constexpr (force_variant_exists(E, P, NOBOND, SOFT)) {
+      d.force_census[force_variant_key(E, P, NOBOND, SOFT)]++;
       hipLaunchKernelGGL((k_force<E, P, NOBOND, SOFT>), dim3(grid), dim3(BLOCK), 0, d.stream, A, bt, d.box, d.f[0], d.f[1], d.f[2], d.partial, d.flags);
+    }
   }, eflag, (parts & 1) != 0, parts == 1, soft && (parts & 1) != 0);
 }
-// f(k_step<the plan's thirteen template arguments, lazy_v as LAZYV before the last three>); false: there is no such instantiation
+// f(k_step<the plan's thirteen template arguments, lazy_v as LAZYV before the last three>, its step_variant_key); false: there
+// is no such instantiation
 template <class F>
 static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   bool found = false;
@@ -1368,7 +1371,8 @@ static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
     with_flags([&](auto L, auto N, auto I, auto W4, auto H) {
       constexpr int W = W4 ? 4 : 1;
       if constexpr (step_variant_exists(L, N, I, true, W, false, H, false, false, false, false, true, false, false, true)) {
-        f(k_step<L, N, I, true, W, false, H, false, false, false, false, true, false, false, true>);
+        f(k_step<L, N, I, true, W, false, H, false, false, false, false, true, false, false, true>,
+          step_variant_key(L, N, I, true, W, false, H, false, false, false, false, true, false, false, true));
         found = true;
       }
     }, p.langevin, p.next, p.ident, p.lpb == 4, p.ahead);
@@ -1381,7 +1385,8 @@ static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
     with_flags([&](auto L, auto N, auto I, auto W4, auto H) {
       constexpr int W = W4 ? 4 : 1;
       if constexpr (step_variant_exists(L, N, I, true, W, false, H, false, false, false, false, false, false, true)) {
-        f(k_step<L, N, I, true, W, false, H, false, false, false, false, false, false, true>);
+        f(k_step<L, N, I, true, W, false, H, false, false, false, false, false, false, true>,
+          step_variant_key(L, N, I, true, W, false, H, false, false, false, false, false, false, true));
         found = true;
       }
     }, p.langevin, p.next, p.ident, p.lpb == 4, p.ahead);
@@ -1389,7 +1394,10 @@ static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
   }
   with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z, auto WL, auto SF) {
     constexpr int W = W4 ? 4 : 1;
-    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL, SF)) { f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL, SF>); found = true; }
+    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL, SF)) {
+      f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL, SF>, step_variant_key(L, N, I, P, W, D, H, G, E, R, Z, WL, SF));
+      found = true;
+    }
   }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v, p.wall, p.soft);
   return found;
 }
@@ -1438,8 +1446,9 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
   // permuted first.  (a launch that stores nothing - a list overflowed - is undone as a whole: undo_step_swap)
   const bool lazy_v = d.v_pending && takes_pending_v(p, d.dd != 0);
   if (!lazy_v) settle_velocities(d);
-  const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel) {
+  const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel, int key) {
     S.indents = itab;
+    d.step_census[key]++;      // (host memory: the launch census, DeviceState::step_census)
     hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, S,
                           d.f[0], d.f[1], d.f[2], d.pos_tmp, d.xhold);
   });
@@ -1496,7 +1505,7 @@ static void test_step_plan(int n_owned, int decomposed, const int *req, int wall
   r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
   r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0; r.ext = ext != 0; r.indents = indents;
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
-  const bool known = p.fused && with_step_kernel(p, false, [](auto) {});
+  const bool known = p.fused && with_step_kernel(p, false, [](auto, int) {});
   const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
                      p.diag_bits, (int)p.lds_pad, known, p.wall, takes_pending_v(p, decomposed != 0)};
   for (int k = 0; k < 18; k++) out[k] = v[k];
@@ -1523,14 +1532,16 @@ extern "C" void lammps_le_test_step_plan_soft(int n_owned, int decomposed, const
 // the hook above, then [19] = StepPlan::ext and [20] = count_step_variants(), the number of instantiations the dispatchers hold
 extern "C" void lammps_le_test_step_plan_ext(int n_owned, int decomposed, const int *req, int *out) {
   test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19);
-  out[20] = count_step_variants();
+  constexpr int variants = count_step_variants();      // (at compile time: the sweeps of the host tests call this a million times)
+  out[20] = variants;
 }
 // fifteen inputs, req[14] = indenters (StepRequest::indents); the 21 outputs of the hook above, then [21] = StepPlan::indent and
 // [22] = count_all_step_variants(), the number of instantiations with the indent variants
 extern "C" void lammps_le_test_step_plan_indent(int n_owned, int decomposed, const int *req, int *out) {
   test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19, req[14], out + 21);
-  out[20] = count_step_variants();
-  out[22] = count_all_step_variants();
+  constexpr int variants = count_step_variants(), all_variants = count_all_step_variants();
+  out[20] = variants;
+  out[22] = all_variants;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -120,7 +120,10 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
 }
 
 // The instantiations of k_step that exist, by its template arguments (what plan_step plans with; implies the
-// static_asserts inside k_step): 24 + 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 153
+// static_asserts inside k_step): 24 + 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 153.  To exist is to be compiled and to be held
+// by the dispatcher; it is NOT to be launched: Engine::iterate asks for a plan with next = false on a thermo step only, so
+// 84 of the 177 below are never the answer to a request of the engine ("Launch census"; the launches of a
+// handle are counted by their step_variant_key, tests/test_step_census_cpu.py holds the set that can be launched)
 constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
                                    bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false) {
   if (INDENT) return WALL && P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !SOFT && !EXT && (LPB == 1 || AHEAD);   // fix indent inside the wall variant: L, N, I x three shapes = 24
@@ -150,6 +153,35 @@ constexpr int count_all_step_variants() {
   return c;
 }
 static_assert(count_all_step_variants() == 177, "the set of k_step instantiations changed");
+
+// The launch census (DeviceState::step_census, force_census): one integer per instantiation, made of the fifteen template
+// arguments in the bit order of count_step_variants's m - L 0, N 1, I 2, P 3, LPB == 4 4, DIAG 5, AHEAD 6, ANG 7, EF 8,
+// GRP 9, LAZYV 10, WALL 11, SOFT 12, EXT 13, INDENT 14.
+constexpr int STEP_KEY_BITS = 15, STEP_KEY_SPACE = 1 << STEP_KEY_BITS;
+constexpr int step_variant_key(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
+                               bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false) {
+  return (int)L | (int)N << 1 | (int)I << 2 | (int)P << 3 | (int)(LPB == 4) << 4 | (int)DIAG << 5 | (int)AHEAD << 6 | (int)ANG << 7 |
+         (int)EF << 8 | (int)GRP << 9 | (int)LAZYV << 10 | (int)WALL << 11 | (int)SOFT << 12 | (int)EXT << 13 | (int)INDENT << 14;
+}
+// the fifteen arguments of a key, in the order of k_step's template (flags[4] = LPB as 1 | 4)
+constexpr void step_key_decode(int key, int flags[STEP_KEY_BITS]) {
+  for (int b = 0; b < STEP_KEY_BITS; b++) flags[b] = (key >> b) & 1;
+  flags[4] = flags[4] ? 4 : 1;
+}
+constexpr bool step_key_exists(int key) {
+  if (key < 0 || key >= STEP_KEY_SPACE) return false;
+  int f[STEP_KEY_BITS] = {};
+  step_key_decode(key, f);
+  return step_variant_exists(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14]);
+}
+// ... and of k_force<E, P, NOBOND, SOFT> (launch_force): E 0, P 1, NOBOND 2, SOFT 3.  Pairs only and pair_style soft need the
+// pair part: 8 + 2 = 10 instantiations
+constexpr int FORCE_KEY_BITS = 4, FORCE_KEY_SPACE = 1 << FORCE_KEY_BITS;
+constexpr bool force_variant_exists(bool E, bool P, bool NOBOND, bool SOFT) { return (void)E, (P || !NOBOND) && (P || !SOFT); }
+constexpr int force_variant_key(bool E, bool P, bool NOBOND, bool SOFT) { return (int)E | (int)P << 1 | (int)NOBOND << 2 | (int)SOFT << 3; }
+constexpr bool force_key_exists(int key) {
+  return key >= 0 && key < FORCE_KEY_SPACE && force_variant_exists(key & 1, key & 2, key & 4, key & 8);
+}
 
 // The launch of this plan takes the velocities a rebuild left in the old order (DeviceState::v_pending): the throughput shape
 // of the kernel, in one launch over every bead of one GPU, with no diagnostic launch in front of it.  Engine::iterate asks

@@ -10,7 +10,8 @@ from force_inputs import INPUTS, script
 STEPS = 12
 LANGEVIN_SEED = 48611
 FIXES = {"nve": "fix 1 all nve\n", "group": "group mobile type 1\nfix 1 mobile nve\n",
-         "langevin": "fix 1 all nve\nfix 2 all langevin 1.0 1.0 1.0 %d\n" % LANGEVIN_SEED}
+         "langevin": "fix 1 all nve\nfix 2 all langevin 1.0 1.0 1.0 %d\n" % LANGEVIN_SEED,
+         "group-langevin": "group mobile type 1\nfix 1 mobile nve\nfix 2 all langevin 1.0 1.0 1.0 %d\n" % LANGEVIN_SEED}
 THERMO_KEYS = ("evdwl", "ebond", "eangle", "pe", "ke", "temp", "press", "pxx", "pyy", "pzz", "pxy", "pxz", "pyz")
 ROW_KEYS = ("temp", "epair", "emol", "etotal", "press")          # columns 1 .. 5 of the engine's thermo_history()
 RUN0_CEILING = 1e-12                                             # the project's bound for single evaluations
@@ -68,7 +69,7 @@ def thermo_of(name, ev, v, norm):
 def reference_trajectory(name, fixes="nve"):
     from oracle import ranmars_stream
     S, x, v, img = reference_system(name, fixes)
-    u = ranmars_stream(LANGEVIN_SEED, 3 * S.n * (STEPS + 1)) if fixes == "langevin" else None
+    u = ranmars_stream(LANGEVIN_SEED, 3 * S.n * (STEPS + 1)) if "langevin" in fixes else None
     return S.trajectory(x, v, img, STEPS, u)
 
 

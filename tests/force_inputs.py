@@ -111,6 +111,18 @@ def offset(pinned=False):
 
 
 # ------------------------------------------------------------------------------------------------
+# census: the geometry of offset at 2145 beads (33 wavefronts and 33 beads: with one lane per bead nine workgroups, a count
+# the launch grid pads; far under the 50000 beads up to which four lanes share a bead) - the input of the launch-census rows
+# that carry a wall, an indenter, a tether or another pair style (census_runs.py, whose reference prunes the candidate pairs:
+# at this size the plain brute force costs seven seconds an evaluation)
+# ------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def census():
+    s = translate(lattice(11, 13, 15, seed=23), OFFSET_ORIGIN)
+    return dict(system=hot(displace(s), 5.0), force_field=FENE + WCA)
+
+
+# ------------------------------------------------------------------------------------------------
 # types: three atom types, per-pair cutoffs 1.0 .. 2.5 without a shift - a pair on the wrong side of a cutoff shows
 # ------------------------------------------------------------------------------------------------
 TYPES_FF = FENE + """pair_style lj/cut 2.5
@@ -275,10 +287,10 @@ def aligned():
     return dict(system=translate(s, OFFSET_ORIGIN), force_field=ALIGNED_FF)
 
 
-INPUTS = {"tiny": tiny, "aligned": aligned, "offset": offset, "offset-pinned": lambda: offset(True), "types": types, "hubs": hubs,
+INPUTS = {"tiny": tiny, "aligned": aligned, "offset": offset, "census": census, "offset-pinned": lambda: offset(True), "types": types, "hubs": hubs,
           "hubs-harmonic": lambda: dict(hubs(), force_field=HUBS_HARMONIC_FF),
           "angles-harmonic": lambda: angles("harmonic"), "angles-cosine": lambda: angles("cosine"), "fene-large": fene_large}
 # which bond-image path the engine takes (stat bond_minimg): the frozen image words unless every bond style is FENE and the
 # shortest box edge exceeds four times the largest R0
-BOND_MINIMG = {"tiny": 0, "offset": 0, "offset-pinned": 0, "types": 0, "hubs": 0, "hubs-harmonic": 0, "aligned": 0, "angles-harmonic": 0, "angles-cosine": 0,
+BOND_MINIMG = {"tiny": 0, "offset": 0, "census": 0, "offset-pinned": 0, "types": 0, "hubs": 0, "hubs-harmonic": 0, "aligned": 0, "angles-harmonic": 0, "angles-cosine": 0,
                "fene-large": 1}

@@ -29,6 +29,8 @@ The statements of the reference program each formula was read from (paths below 
   wrap             domain.cpp Domain::remap / pbc: x -+ prd with the image flag counting the other way
 """
 import collections
+import contextlib
+import sys
 
 import numpy as np
 
@@ -45,6 +47,38 @@ TWO_1_3 = LD(2) ** (LD(1) / LD(3))
 
 def ld(a):
     return np.asarray(a, dtype=LD)
+
+
+def _constants():
+    global SMALL, PI, TWO_1_3
+    SMALL, PI, TWO_1_3 = LD("0.001"), LD("3.14159265358979323846264338327950288"), LD(2) ** (LD(1) / LD(3))
+
+
+@contextlib.contextmanager
+def precision(dtype):
+    """The dtype switch of the restatement: inside the block this module and the modules that add terms to it (soft_reference,
+    wall_reference, extforce_reference, indent_reference, as far as they are loaded) compute in `dtype` instead of long double -
+    the same statements in the same order.  A System has to be built AND used inside the block.  What a run in np.float64 is off
+    by from the long-double run is the rounding of this restatement in the engine's own number format: the figure that stands
+    in for the oracle's deviation (force_compare.bound) where the oracle has no such term."""
+    global LD
+    mods = [sys.modules[m] for m in ("soft_reference", "wall_reference", "extforce_reference", "indent_reference") if m in sys.modules]
+    keep = LD
+    try:
+        LD = dtype
+        _constants()
+        for m in mods:
+            m.LD = dtype
+            if hasattr(m, "PI"):
+                m.PI = PI
+        yield
+    finally:
+        LD = keep
+        _constants()
+        for m in mods:
+            m.LD = keep
+            if hasattr(m, "PI"):
+                m.PI = PI
 
 
 # ------------------------------------------------------------------------------------------------
@@ -416,13 +450,17 @@ class System:
     def unwrapped(self, x, img):
         return ld(x) + ld(img) * self.prd
 
-    def trajectory(self, x0, v0, img0, nsteps, uniforms=None, topology=None):
+    def trajectory(self, x0, v0, img0, nsteps, uniforms=None, topology=None, extra=None):
         """Velocity Verlet from the state read_data leaves (x0 inside the box, image flags img0): setup, then nsteps steps.
         Returns per step (0 .. nsteps) the unwrapped positions, velocities, thermo rows and min |r^2 - cut^2|, and the
         force array of the last step (with the Langevin force, as the engine's f holds it).
         topology(step) -> (bonds, angles): the tables in force at the force evaluation of `step` (a fix that edits them does so
         between the position update and that evaluation); where the answer differs from the previous step's, the bonds, the
-        angles and the pair weights are rebuilt before the evaluation.  Without it the topology is static."""
+        angles and the pair weights are rebuilt before the evaluation.  Without it the topology is static.
+        extra(step, x, img, f) -> f: the hook for force terms of other modules (a wall, an indenter, a tether, a pull) - it takes
+        the positions inside the box, the image flags and the force of the model's own terms at the evaluation of `step` and
+        returns the force with its terms added, before the thermostat's.  The thermo rows stay the model's own (a fix enters
+        them only under fix_modify)."""
         assert self.model.nve
         x, v, img = ld(x0).copy(), ld(v0).copy(), np.asarray(img0, dtype=np.int64).copy()
         dt = LD(self.model.dt)
@@ -442,7 +480,7 @@ class System:
                     self.set_topology(bonds, angles)
                     held[0] = key
             ev = self.evaluate(x)
-            f = ev.f
+            f = ev.f if extra is None else extra(step, x, img, ev.f)
             if self.model.langevin:
                 f = f + self.langevin_force(v, uniforms[step * n3:(step + 1) * n3])
             return ev, f
