@@ -825,14 +825,14 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "velocities_settled") return e->dev ? (double)e->dev->v_settled : 0.0;   // settle_velocities launches since the arrays were allocated
   // time steps of the last run by the path they took: the step kernel (steps_fused_group of them its group variant), its
   // energy variant on a thermo step, the unfused kernels; the three add up to the steps of the run
-  if (k == "steps_fused") return (double)e->steps_fused;
-  if (k == "steps_fused_group") return (double)e->steps_fused_group;
-  if (k == "steps_fused_thermo") return (double)e->steps_fused_thermo;
-  if (k == "steps_unfused") return (double)e->steps_unfused;
-  if (k == "steps_fused_ext") return (double)e->steps_fused_ext;        // of steps_fused: spring/self, addforce, setforce inside the step kernel
-  if (k == "steps_fused_wall") return (double)e->steps_fused_wall;      // of steps_fused: fix wall/region inside the step kernel
-  if (k == "steps_fused_indent") return (double)e->steps_fused_indent;  // of steps_fused: the launch carried an indenter of fix indent
-  if (k == "steps_fused_soft") return (double)e->steps_fused_soft;      // of steps_fused: pair_style soft inside the step kernel
+  if (k == "steps_fused") return (double)e->steps.fused;
+  if (k == "steps_fused_group") return (double)e->steps.fused_group;
+  if (k == "steps_fused_thermo") return (double)e->steps.fused_thermo;
+  if (k == "steps_unfused") return (double)e->steps.unfused;
+  if (k == "steps_fused_ext") return (double)e->steps.fused_ext;        // of steps_fused: spring/self, addforce, setforce inside the step kernel
+  if (k == "steps_fused_wall") return (double)e->steps.fused_wall;      // of steps_fused: fix wall/region inside the step kernel
+  if (k == "steps_fused_indent") return (double)e->steps.fused_indent;  // of steps_fused: the launch carried an indenter of fix indent
+  if (k == "steps_fused_soft") return (double)e->steps.fused_soft;      // of steps_fused: pair_style soft inside the step kernel
   if (k == "pair_table_copies") return (double)e->pair_table_copies;    // fix adapt: copies of the pair table in the middle of runs
   // the last `minimize`: iterations, force evaluations, index into Min::stopstrings, the last line search's alpha, times the host
   // waited for the device, list builds; and the numbers of its stats block
@@ -968,15 +968,36 @@ extern "C" int lammps_le_test_indent_table(void *handle, long begin, long end, l
   struct InRun { Engine *e; bool was; long b0, e0, n0; InRun(Engine *en) : e(en), was(en->in_run), b0(en->beginstep), e0(en->endstep), n0(en->ntimestep) {}
                  ~InRun() { e->in_run = was; e->beginstep = b0; e->endstep = e0; e->ntimestep = n0; } } keep(e);
   e->init();
-  e->build_indent_list();
+  e->postforce.build(e->fixes, e->natoms);
   e->in_run = true; e->beginstep = begin; e->endstep = end; e->ntimestep = now;
-  const IndentTable t = e->indent_table();
+  const IndentTable t = e->postforce.indent_table();
   for (int k = 0; k < t.n; k++) {
     const IndentEntry &o = t.e[k];
     const double row[10] = {(double)o.kind, (double)o.axis, (double)o.side, (double)o.groupbit, (double)o.phase, o.k, o.ctr[0], o.ctr[1], o.ctr[2], o.r};
     for (int c = 0; c < 10; c++) out[10 * k + c] = row[c];
   }
   return t.n;
+  END_CAPTURE
+  return -1;
+}
+
+// test hook (not part of the reference surface, not declared in include/lammps_le.h): what the one walk over the fixes makes of
+// the script, without a device - the init() of a run command, then PostForce::build.  out: per post-force fix, in fix order, four
+// numbers - family (0 wall/region, 1 indent, 2 spring/self | addforce | setforce), index within its table, phase, group bit.
+// Returns the number of rows, or -1 with the error recorded on the handle
+extern "C" int lammps_le_test_post_force_rows(void *handle, int *out) {
+  BEGIN_CAPTURE
+  e->init();
+  PostForce &pf = e->postforce;
+  pf.build(e->fixes, e->natoms);
+  int n = 0;
+  auto put = [&](int family, size_t k, int phase, int bit) { int *r = out + 4 * n++; r[0] = family; r[1] = (int)k; r[2] = phase; r[3] = bit; };
+  for (auto &f : e->fixes) {
+    for (size_t k = 0; k < pf.wall_fixes.size(); k++) if (pf.wall_fixes[k] == f.get()) put(0, k, pf.walltab.w[k].after_langevin, pf.walltab.w[k].groupbit);
+    for (size_t k = 0; k < pf.indent_fixes.size(); k++) if (pf.indent_fixes[k] == f.get()) put(1, k, pf.indent_phase[k], f->groupbit);
+    for (size_t k = 0; k < pf.forceop_fixes.size(); k++) if (pf.forceop_fixes[k] == f.get()) put(2, k, pf.forceoptab.e[k].phase, pf.forceoptab.e[k].groupbit);
+  }
+  return n;
   END_CAPTURE
   return -1;
 }

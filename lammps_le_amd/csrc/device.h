@@ -452,29 +452,27 @@ void launch_angle_list(DeviceState &d);       // at every reneighbor of a run wi
 void upload_angle_table(DeviceState &d, const AngleTable &at);   // before the first fused step of a run with an angle style
 void reduce_angle_partials(DeviceState &d, double *out8);
 // fix wall/region (kernels_md.hip): the table of a run; the walls of one place among the post-force fixes added to f (eflag:
-// with the ten block sums per wall); those sums on the host, rows of 16 per wall of the table (synchronises the stream)
+// with the ten block sums per wall)
 void upload_wall_table(DeviceState &d, const WallTable &wt);
 void launch_wall(DeviceState &d, const WallTable &wt, int phase, bool eflag);
-void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out);
 // fix indent (kernels_md.hip): the rows of block sums of a run; the indenters of one place among the post-force fixes added to f -
-// the table goes by value with the launch (eflag: with the four block sums per indenter); those sums on the host, rows of 16
-// per indenter (synchronises the stream)
+// the table goes by value with the launch (eflag: with the four block sums per indenter)
 void reserve_indent_partials(DeviceState &d);
 void launch_indent(DeviceState &d, const IndentTable &it, int phase, bool eflag);
-void reduce_indent_partials(DeviceState &d, int nindent, double *out);
 // fix spring/self | addforce | setforce (kernels_md.hip): the table of a run with the origin blocks (`origins[k]`: the host
 // block [natoms][3] of entry k, null for an entry that has none; the table's entries get the device addresses); the entries of
-// one phase applied to f in table order (`active`: bit k - entry k acts on this step; eflag: with the ten block sums per
-// entry); those sums on the host, rows of 16 per entry (synchronises the stream)
+// one phase applied to f in table order (`active`: bit k - entry k acts on this step; eflag: with the ten block sums per entry)
 void upload_forceop_table(DeviceState &d, ForceOpTable &ft, const double *const *origins, int natoms);
 void launch_fixforce(DeviceState &d, const ForceOpTable &ft, int phase, unsigned active, bool eflag);
-void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *out);
+// the block sums of one of these families (wall_partial | indent_partial | forceop_partial) on the host: rows of 16 per wall,
+// indenter or entry (synchronises the stream)
+void reduce_rows(DeviceState &d, double *partial, int n, double *out);
 // reductions: returns sums of `partial` columns on the host (synchronises the stream)
 void reduce_partials(DeviceState &d, double *out16);
 
 // the same sums left in device memory without a copy or a wait (the totals land in the spare row of each table): where they
 // are, for a record that collects them (kernels_min.hip k_min_collect)
-void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, int nindent, bool angles, MinSources &src);
+void enqueue_thermo_sums(DeviceState &d, const PostForce &pf, bool angles, MinSources &src);
 
 // minimize (kernels_min.hip).  min_alloc: the partials and the record, with `vectors` also x0 g h; min_free releases the
 // vectors and, with `all`, the rest.

@@ -758,10 +758,6 @@ std::string Engine::group_signature() const {
   for (auto &f : fixes) if (f->groupbit != 1) sig += f->id + ":" + f->style + ":" + std::to_string(f->groupbit) + ";";
   return sig;
 }
-static bool fixes_on_groups(Engine *e) {
-  for (auto &f : e->fixes) if (f->groupbit != 1) return true;
-  return false;
-}
 static bool md_fixes_on_groups(Engine *e) {      // fix nve / fix langevin: the ones the fused step kernel stands for
   for (auto &f : e->fixes)
     if (f->groupbit != 1 && (dynamic_cast<FixNVE *>(f.get()) || dynamic_cast<FixLangevin *>(f.get()))) return true;
@@ -925,129 +921,12 @@ static void langevin_post_force(Engine *e, FixLangevin *lg, bool fuse_final) {
   rng_langevin_consumed(*e->dev);
 }
 
-// fix wall/region: the table of this run, in fix order; a wall defined behind fix langevin acts behind it (the reference runs
-// the post_force hooks in the order the fixes were defined, src/modify.cpp:463-466)
-void Engine::build_wall_table() {
-  walltab = WallTable{};
-  wall_fixes.clear();
-  bool behind = false;
-  for (auto &f : fixes) {
-    if (dynamic_cast<FixLangevin *>(f.get())) behind = true;
-    auto *w = dynamic_cast<FixWallRegion *>(f.get());
-    if (!w) continue;
-    WallEntry e = w->entry();
-    e.after_langevin = behind ? 1 : 0;
-    walltab.w[walltab.n++] = e;
-    wall_fixes.push_back(w);
-  }
-}
-void Engine::wall_post_force(int phase, bool eflag) {
-  if (walltab.n) launch_wall(*dev, walltab, phase, eflag);
-  // fix indent behind the walls of its place: the geometry of this force evaluation, once for both places
-  if (!indent_fixes.empty()) {
-    if (phase == 0) indent_now = indent_table();
-    launch_indent(*dev, indent_now, phase, eflag);
-  }
-  forceop_post_force(phase, eflag);      // within a phase the walls act first (build_forceop_table holds the scripts to that)
-}
-
-// fix indent: the fixes of this run in fix order, each with its place relative to fix langevin (as the walls)
-void Engine::build_indent_list() {
-  indent_fixes.clear();
-  indent_phase.clear();
-  indent_now = IndentTable{};
-  int phase = 0;
-  for (auto &f : fixes) {
-    if (dynamic_cast<FixLangevin *>(f.get())) phase = 1;
-    auto *o = dynamic_cast<FixIndent *>(f.get());
-    if (!o) continue;
-    if ((int)indent_fixes.size() >= INDENT_MAX) throw LammpsError("internal: more than INDENT_MAX fix indent instances");
-    indent_fixes.push_back(o);
-    indent_phase.push_back(phase);
-  }
-}
-// The table of one force evaluation: FixIndent::post_force's head for every indenter - the formulas with ntimestep as it stands,
-// the centre remapped - evaluated on the host between two launches
-IndentTable Engine::indent_table() {
-  IndentTable t{};
-  for (size_t k = 0; k < indent_fixes.size(); k++) {
-    IndentEntry e = indent_fixes[k]->entry();
-    e.phase = indent_phase[k];
-    t.e[t.n++] = e;
-  }
-  return t;
-}
-static int indents_request(const Engine *e) {      // StepRequest::indents
-  if (e->indent_fixes.empty()) return 0;
-  for (auto *o : e->indent_fixes) if (o->groupbit != 1) return 2;
-  return 1;
-}
-static bool indents_behind_langevin(const Engine *e) {
-  for (int ph : e->indent_phase) if (ph) return true;
-  return false;
-}
-
-// fix spring/self | addforce | setforce: the table of this run, in fix order (the order the reference runs post_force in, which
-// setforce's overwrite and the foriginal sums of addforce / setforce see).  The kernels run the walls of a phase ahead of these
-// entries, so an addforce or setforce defined ahead of a wall on the same side of fix langevin would see the wrong force: refused.
-// spring/self adds a force that depends on the position alone and may stand anywhere.
-void Engine::build_forceop_table() {
-  forceoptab = ForceOpTable{};
-  forceop_fixes.clear();
-  forceoptab.stride = natoms + 1;
-  int phase = 0;
-  bool order_matters[2] = {false, false};     // an addforce / setforce was seen in this phase
-  for (auto &f : fixes) {
-    if (dynamic_cast<FixLangevin *>(f.get())) phase = 1;
-    if (dynamic_cast<FixWallRegion *>(f.get()) && order_matters[phase])
-      throw LammpsError("MI355X engine: fix " + f->id + " (wall/region) is defined behind a fix addforce or setforce on the same side of "
-                        "fix langevin; define the wall first");
-    if (dynamic_cast<FixIndent *>(f.get()) && order_matters[phase])
-      throw LammpsError("MI355X engine: fix " + f->id + " (indent) is defined behind a fix addforce or setforce on the same side of "
-                        "fix langevin; define the indenter first");
-    auto *o = dynamic_cast<FixForceOp *>(f.get());
-    if (!o) continue;
-    if (forceoptab.n >= FORCEOP_MAX) throw LammpsError("internal: more than FORCEOP_MAX force fixes");
-    ForceOpEntry e = o->entry();
-    e.phase = phase;
-    if (o->kind != FORCEOP_SPRING) order_matters[phase] = true;
-    forceoptab.e[forceoptab.n++] = e;
-    forceop_fixes.push_back(o);
-  }
-}
-unsigned Engine::forceop_active() const {
-  unsigned m = 0;
-  for (int k = 0; k < forceoptab.n; k++) if (ntimestep % forceoptab.e[k].every == 0) m |= 1u << k;
-  return m;
-}
-// An addforce with `every N` reports, on a thermo step it skips, the sums of the last step on which it acted: that step takes the
-// unfused kernels with the block sums, like a thermo step.  True when `ntimestep` is such a step: an entry with N > 1 acts now and
-// the next thermo step (a multiple of `thermo`, or the end of the run) comes before it acts again
-static bool forceop_sums_due(const Engine *e) {
-  for (int k = 0; k < e->forceoptab.n; k++) {
-    const long every = e->forceoptab.e[k].every;
-    if (every <= 1 || e->ntimestep % every) continue;
-    long next = e->endstep;
-    if (e->thermo_every > 0) next = std::min(next, (e->ntimestep / e->thermo_every + 1) * (long)e->thermo_every);
-    if (next > e->ntimestep && next - e->ntimestep < every) return true;
-  }
-  return false;
-}
-void Engine::forceop_post_force(int phase, bool eflag) {
-  if (forceoptab.n) launch_fixforce(*dev, forceoptab, phase, forceop_active(), eflag);
-}
-static bool forceops_behind_langevin(const Engine *e) {
-  for (int k = 0; k < e->forceoptab.n; k++) if (e->forceoptab.e[k].phase) return true;
-  return false;
-}
-static int walls_request(const Engine *e) {      // StepRequest::walls
-  if (!e->walltab.n) return 0;
-  for (int k = 0; k < e->walltab.n; k++) if (e->walltab.w[k].groupbit != 1) return 2;
-  return 1;
-}
-static bool walls_behind_langevin(const Engine *e) {
-  for (int k = 0; k < e->walltab.n; k++) if (e->walltab.w[k].after_langevin) return true;
-  return false;
+// Modify::post_force for the fixes that act on the forces (src/modify.cpp:463-466 runs the hooks in fix order; PostForce::build
+// holds the scripts to the order the kernels run them in): the one sequence of setup, iterate, r-RESPA and the minimiser
+void Engine::post_force_sequence(FixLangevin *lg, bool eflag, bool fuse_final) {
+  postforce.run(*dev, ntimestep, 0, eflag);
+  if (lg) langevin_post_force(this, lg, fuse_final);
+  postforce.run(*dev, ntimestep, 1, eflag);
 }
 
 // fix adapt (src/fix_adapt.cpp:495-515, :536-665): at setup of a run every fix adapt sets its values, in the loop those whose
@@ -1108,16 +987,11 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
   DeviceState &d = *dev;
   TypeTables tt = make_tables(this, nullptr);
   if (!ke_summed) launch_ke(d, tt);       // (the energy variant of the step kernel has summed the kinetic energy as well)
-  // behind the sixteen sums of the force kernel: the ten of every wall (rows of 16), in the same all-reduce
-  // ... and behind those the ten of every spring/self, addforce and setforce
-  // ... and behind those the four of every indenter
-  double s[16 + 16 * WALL_MAX + 16 * FORCEOP_MAX + 16 * INDENT_MAX];
+  // behind the sixteen sums of the force kernel the rows of the post-force fixes (PostForce), in the same all-reduce
+  double s[PostForce::SUMS_MAX];
   reduce_partials(d, s);
-  const int nwall = walltab.n, nops = forceoptab.n, nind = (int)indent_fixes.size();
-  if (nwall) reduce_wall_partials(d, walltab, s + 16);
-  if (nops) reduce_fixforce_partials(d, forceoptab, s + 16 + 16 * nwall);
-  if (nind) reduce_indent_partials(d, nind, s + 16 + 16 * (nwall + nops));
-  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * (nwall + nops + nind));
+  postforce.reduce(d, s);
+  if (world > 1) comm->allreduce_host_sum(s, 16 + 16 * postforce.sum_rows());
   double a8[8], k6[6];
   const bool ang = angles_active();
   if (ang) {
@@ -1150,32 +1024,8 @@ ThermoRow Engine::eval_thermo(bool ke_summed) {
 }
 
 ThermoRow Engine::thermo_from_sums(const double *s, const double *a8, const double *k6) {
-  const int nwall = walltab.n, nops = forceoptab.n;
   double efix = 0.0, vfix[6] = {0, 0, 0, 0, 0, 0};      // Modify::thermo_energy (src/compute_pe.cpp:102), the fixes of compute_pressure.cpp:201-220
-  for (int k = 0; k < nwall; k++) {
-    FixWallRegion *w = wall_fixes[k];
-    const double *ws = s + 16 + 16 * k;
-    for (int c = 0; c < 4; c++) w->ewall[c] = ws[c];
-    for (int c = 0; c < 6; c++) w->virial[c] = ws[4 + c];
-    if (w->thermo_energy) efix += w->ewall[0];
-    if (w->thermo_virial) for (int c = 0; c < 6; c++) vfix[c] += w->virial[c];
-  }
-  for (int k = 0; k < nops; k++) {
-    FixForceOp *o = forceop_fixes[k];
-    // (an addforce that skipped this step - `every` - returned before it touched its sums, src/fix_addforce.cpp:243: the rows
-    //  of block sums are then those of the last step on which it acted, which forceop_sums_due had evaluated with them)
-    //  The six virial terms are different: v_tally runs only on a step that wants the virial, so after a skipped thermo step
-    //  the reference's array still holds what the last thermo step on which the fix acted left (:247-248, :292-300)
-    const bool acted = (forceop_active() >> k) & 1u;
-    for (int c = 0; c < FORCEOP_COLS; c++) if (c < 4 || acted) o->sums[c] = s[16 + 16 * (nwall + k) + c];
-    if (o->thermo_energy) efix += o->compute_scalar();
-    if (o->thermo_virial) for (int c = 0; c < 6; c++) vfix[c] += o->sums[4 + c];
-  }
-  for (size_t k = 0; k < indent_fixes.size(); k++) {      // FixIndent::compute_scalar / compute_vector; no virial (virial_flag 0)
-    FixIndent *o = indent_fixes[k];
-    for (int c = 0; c < INDENT_COLS; c++) o->indenter[c] = s[16 + 16 * (nwall + nops + (int)k) + c];
-    if (o->thermo_energy) efix += o->indenter[0];
-  }
+  postforce.take_sums(s, ntimestep, efix, vfix);
   ThermoRow r{};
   r.step = ntimestep;
   double dof = 3.0 * natoms - 3.0;                       // src/compute_temp.cpp:60-68
@@ -1331,14 +1181,12 @@ void Engine::setup() {
   double s1 = wall();
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = steps_fused_indent = 0;
+  steps.reset();
   adapt_apply(true);                              // FixAdapt::setup_pre_force
   compute_forces(true);
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
-  wall_post_force(0, true);                       // FixWallRegion::setup -> post_force (src/fix_wall_region.cpp:200-209), in fix order
-  if (lg) langevin_post_force(this, lg, false);   // FixLangevin::setup -> post_force (:372-373)
-  wall_post_force(1, true);
+  post_force_sequence(lg, true, false);           // FixWallRegion::setup -> post_force (src/fix_wall_region.cpp:200-209), FixLangevin::setup -> post_force (:372-373)
   double s2 = wall();
   last_thermo = eval_thermo();
   double s3 = wall();
@@ -1376,9 +1224,9 @@ void Engine::iterate(long nsteps) {
   StepRequest rq;
   rq.langevin = lg != nullptr; rq.ident = d.ident_order; rq.pair = pair_force(); rq.soft = pair_soft; rq.angles = ang;
   rq.nvebit = fusable ? nbits[0] : 1; rq.lgbit = lg ? lg->groupbit : 1;
-  rq.walls = walls_request(this);
-  rq.indents = indents_request(this);
-  rq.ext = forceoptab.n > 0;
+  rq.walls = postforce.walls_request();
+  rq.indents = postforce.indents_request();
+  rq.ext = postforce.ext();
   bool pre_integrated = false;
   const bool adapting = have_adapt();
   // halo/compute overlap issues the per-step halo on a second stream.  With RCCL that means two streams feeding ONE
@@ -1400,7 +1248,7 @@ void Engine::iterate(long nsteps) {
     bool eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0);
     const bool restart_now = restart_every > 0 && ntimestep % restart_every == 0;
     const bool dump_now = (!dumps.empty() && dump_due(ntimestep)) || restart_now;   // needs the complete state of this step: unfused path
-    const bool ext_sums = !eflag && forceop_sums_due(this);      // (the fixes' block sums of this step are wanted: unfused, no thermo row)
+    const bool ext_sums = !eflag && postforce.forceop_sums_due(ntimestep, endstep, thermo_every);      // (the fixes' block sums of this step are wanted: unfused, no thermo row)
     TypeTables tt = make_tables(this, lg);
     // the plan of this step: a dump / restart needs the complete state of the step, which the unfused kernels leave
     rq.next = it + 1 < nsteps; rq.thermo = eflag || ext_sums; rq.which = -1; rq.check = false;
@@ -1408,12 +1256,12 @@ void Engine::iterate(long nsteps) {
     StepPlan plan = plan_now();
     StepArgs sa;
     sa.bt = &bondtab; sa.special_lj = special_lj; sa.tt = &tt; sa.dtv = dt; sa.triggersq = triggersq;
-    sa.ext_active = forceop_active();      // (of the step whose forces the launch computes: this one, not its NEXT half's)
+    sa.ext_active = postforce.forceop_active(ntimestep);      // (of the step whose forces the launch computes: this one, not its NEXT half's)
     // fix indent: the geometry of this step - evaluated here, between two launches, and carried by the launch itself.  (The
     // plan is taken again behind the rebuild with `check` and `cells` set; whether it is fused with the wall flag depends on
     // neither, so this answer holds for the launch)
     const bool indents_fused = plan.fused && plan.indent;
-    if (indents_fused) { indent_now = indent_table(); sa.indents = &indent_now; }
+    if (indents_fused) { postforce.indent_now = postforce.indent_table(); sa.indents = &postforce.indent_now; }
     stamp();
     if (!pre_integrated) {
       bool will_check = neigh_check && (ago + 1 >= neigh_delay) && ((ago + 1) % neigh_every == 0);
@@ -1481,12 +1329,12 @@ void Engine::iterate(long nsteps) {
       if (timed) d.ev_used++;
       if (lg) rng_langevin_consumed(d);
       pre_integrated = next;
-      steps_fused++;
-      if (plan.grp) steps_fused_group++;
-      if (plan.wall && walltab.n) steps_fused_wall++;
-      if (plan.indent) steps_fused_indent++;
-      if (plan.soft) steps_fused_soft++;
-      if (plan.ext) steps_fused_ext++;
+      steps.fused++;
+      if (plan.grp) steps.fused_group++;
+      if (plan.wall && postforce.walltab.n) steps.fused_wall++;
+      if (plan.indent) steps.fused_indent++;
+      if (plan.soft) steps.fused_soft++;
+      if (plan.ext) steps.fused_ext++;
       stamp(T_PAIR);          // the fused kernel: pair + bond + post_force + final_integrate (+ next initial_integrate)
     } else if (plan.fused) {
       // a thermo step without dumps: the step kernel's energy variant - forces, energies, virial, post_force and
@@ -1497,7 +1345,7 @@ void Engine::iterate(long nsteps) {
       launch_step(d, plan, sa);
       if (lg) rng_langevin_consumed(d);
       pre_integrated = false;
-      steps_fused_thermo++;
+      steps.fused_thermo++;
       stamp(T_PAIR);
       last_thermo = eval_thermo(true);
       thermo_log.push_back(last_thermo);
@@ -1507,15 +1355,12 @@ void Engine::iterate(long nsteps) {
       if (!finish_reneighbor()) regrow_lists();
       if (d.dd) dd_halo_wait(d);
       compute_forces(eflag);
-      steps_unfused++;
+      steps.unfused++;
       stamp(T_PAIR);          // k_force: pair + bond in one pass
       // (Langevin and the final half-kick in one kernel only when both fixes act on the same atoms)
       // fix wall/region at its place among the post-force fixes: before fix langevin, or behind it (no fused half-kick then)
-      wall_post_force(0, eflag || ext_sums);
-      const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag &&
-                                  !walls_behind_langevin(this) && !forceops_behind_langevin(this) && !indents_behind_langevin(this);
-      if (lg) langevin_post_force(this, lg, lg_fused_final);
-      wall_post_force(1, eflag || ext_sums);
+      const bool lg_fused_final = lg && nnve == 1 && nbits[0] == lg->groupbit && langevin_members > 0 && !lg->zeroflag && !postforce.behind_langevin();
+      post_force_sequence(lg, eflag || ext_sums, lg_fused_final);
       if (!lg_fused_final)
         for (int k = 0; k < nnve; k++) launch_final_integrate(d, tt, nbits[k]);
       pre_integrated = false;
@@ -1562,7 +1407,7 @@ void Engine::respa_setup() {                                   // Respa::setup (
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = steps_fused_indent = 0;
+  steps.reset();
   for (int l = 0; l <= top; l++) {
     if (l == top) adapt_apply(true);           // FixAdapt::setup_pre_force_respa: the outermost level only
     respa_level_forces(l);
@@ -1570,11 +1415,9 @@ void Engine::respa_setup() {                                   // Respa::setup (
   }
   FixLangevin *lg = the_langevin(this);
   for (auto &f : fixes) f->setup();
-  if (lg || walltab.n || forceoptab.n || !indent_fixes.empty()) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
+  if (lg || postforce.any()) {   // FixLangevin::setup, respa branch (src/fix_langevin.cpp:372-378): into the outermost level's array;
     launch_flevel_copy(d, d.respa_flevel[top], false, false);     // FixWallRegion::setup likewise (ilevel_respa = the outermost)
-    wall_post_force(0, true);
-    if (lg) langevin_post_force(this, lg, false);
-    wall_post_force(1, true);
+    post_force_sequence(lg, true, false);
     launch_flevel_copy(d, d.respa_flevel[top], true, false);
   }
   compute_forces(true);              // energies and virial of the initial state for the thermo line (forces are reloaded per level)
@@ -1628,10 +1471,8 @@ void Engine::respa_recurse(int l, bool last) {
     stamp(T_PAIR);
     // post_force_respa at the outermost level (src/fix_langevin.cpp:576-579, src/fix_wall_region.cpp:306-309), in fix order; a
     // thermo step also takes the walls' sums (the positions are the step's last)
-    const bool wall_eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0) || forceop_sums_due(this);
-    if (l == top) wall_post_force(0, wall_eflag);
-    if (l == top && lg) langevin_post_force(this, lg, false);
-    if (l == top) wall_post_force(1, wall_eflag);
+    const bool wall_eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0) || postforce.forceop_sums_due(ntimestep, endstep, thermo_every);
+    if (l == top) post_force_sequence(lg, wall_eflag, false);
     for (int k = 0; k < nnve; k++) launch_final_integrate(d, ttl, nbits[k]); // final_integrate_respa (src/fix_nve.cpp:159-163)
     stamp(T_MODIFY);
   }
@@ -1641,7 +1482,7 @@ void Engine::respa_iterate(long nsteps) {                                    // 
   DeviceState &d = *dev;
   for (long it = 0; it < nsteps; it++) {
     ntimestep++;
-    steps_unfused++;
+    steps.unfused++;
     const bool eflag = (ntimestep == endstep) || (thermo_every > 0 && ntimestep % thermo_every == 0);
     const bool restart_now = restart_every > 0 && ntimestep % restart_every == 0;
     const bool dump_now = (!dumps.empty() && dump_due(ntimestep)) || restart_now;
@@ -1709,7 +1550,6 @@ void Engine::run(long nsteps) {
   const bool trace = getenv("LAMMPS_LE_TRACE_RUN") != nullptr;
   double tr0 = wall();
   init();
-  build_forceop_table();      // (beside build_wall_table below, but ahead of the upload: what it refuses needs no device)
   double tr1 = wall();
   begin_run_state();
   double tr2 = wall();
@@ -1765,8 +1605,9 @@ void Engine::run(long nsteps) {
   }
 }
 
-// What `run` and `minimize` share between init() and their setup (the caller has built the table of the force fixes)
+// What `run` and `minimize` share between init() and their setup
 void Engine::begin_run_state() {
+  postforce.build(fixes, natoms);      // (ahead of the upload: what it refuses needs no device)
   rebuild_knobs = RebuildKnobs();
   // (the fixes on groups are not those of the last upload: the masks, the member ranks and the thermostat's member count travel
   // with an upload - also when the last fix on a group has gone and they have to fall back to `all`)
@@ -1779,21 +1620,9 @@ void Engine::begin_run_state() {
   if (!dev_current || !dev || !dev->pos) upload();
   else push_pair_table(false);       // coefficients given since the last run
   group_sig = group_signature();
-  build_wall_table();
   // (decomposed runs: every rank evaluates the beads it owns, the sums join the all-reduce of eval_thermo, and a bead outside a
   //  region ends every rank - the error flag travels with the displacement test's reduction, Engine::decide)
-  // fix indent: its fixes in order; their table travels with the launches, the rows of block sums are reserved here.  The wall
-  // variant of the step kernel reads the wall table whenever it runs: a run with indenters alone gets one with n = 0
-  build_indent_list();
-  dev->indent_count = (int)indent_fixes.size();
-  if (walltab.n || !indent_fixes.empty()) upload_wall_table(*dev, walltab);
-  if (!indent_fixes.empty()) reserve_indent_partials(*dev);
-  // fix spring/self | addforce | setforce: the table (built above) and the origin blocks of the tethers (by tag, whole on every rank)
-  if (forceoptab.n) {
-    std::vector<const double *> origins;
-    for (auto *o : forceop_fixes) origins.push_back(o->kind == FORCEOP_SPRING ? o->xorig.data() : nullptr);
-    upload_forceop_table(*dev, forceoptab, origins.data(), natoms);
-  }
+  postforce.upload(*dev);
   if (dev->dd) dd_fast_halo_switch(*dev);
   for (int k = 1; k <= 3; k++) dev->sflag[k] = special_flag(k);
   set_xhold_alias(*dev, !dev->dd && !rebuild_knobs.no_xhold_alias);

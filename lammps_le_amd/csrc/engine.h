@@ -15,6 +15,7 @@
 
 #include "step_plan.h"
 #include "rebuild_plan.h"
+#include "post_force.h"
 
 namespace lmp_le {
 
@@ -39,10 +40,6 @@ constexpr int NN_NBOND_MASK = 0xFF;          // bond entries of the word: (word 
 // two bits per dimension and bond slot in DeviceState::bshift (0 none, 1 partner at +prd, 2 partner at -prd)
 constexpr int NN_SHIFTED_BIT = 1 << 30;
 constexpr int BSHIFT_BITS = 6;
-constexpr int FORCEOP_MAX = 8;    // fix spring/self | addforce | setforce instances one run can hold (ForceOpTable)
-constexpr int WALL_MAX = 4;        // fix wall/region instances one run can hold (WallTable)
-constexpr int INDENT_MAX = 4;      // fix indent instances one run can hold (IndentTable)
-
 // ---------------------------------------------------------------------------------------------
 // RanMars in exact integer arithmetic (src/random_mars.cpp:29-95; every value is k * 2^-24)
 // ---------------------------------------------------------------------------------------------
@@ -88,66 +85,6 @@ struct AngleTable {  // by-value kernel argument: angle_style harmonic | cosine 
   int style[MAXTYPES + 1];     // 0 none/zero, 1 harmonic, 2 cosine
   double k[MAXTYPES + 1], theta0[MAXTYPES + 1];   // theta0 in radians
 };
-
-// fix wall/region (src/fix_wall_region.cpp): what the kernels need of every wall, built on the host at every `run`
-enum WallStyle { WALL_LJ93 = 0, WALL_LJ126 = 1, WALL_LJ1043 = 2, WALL_HARMONIC = 3, WALL_MORSE = 4 };
-enum WallRegionKind { WALL_BLOCK = 0, WALL_SPHERE = 1, WALL_CYLINDER = 2 };
-struct WallEntry {
-  int kind, interior, axis;   // region: WallRegionKind, side in (1) | out (0), the cylinder's axis (0 x, 1 y, 2 z)
-  int style;                  // WallStyle
-  int groupbit;               // the fix's group (1 = all)
-  int after_langevin;         // the fix is defined behind fix langevin: its force is added after drag and noise
-  double p[6];                // the region's parameters, as Engine::Region::p
-  double coeff[8];            // coeff1 .. coeff7 of FixWallRegion::init at [1] .. [7]
-  double offset, cutoff;
-  double epsilon, sigma, alpha;   // harmonic: epsilon; morse: D0 (epsilon), r0 (sigma), alpha
-};
-struct WallTable {
-  int n;
-  WallEntry w[WALL_MAX];
-};
-
-// fix indent (src/fix_indent.cpp): what the kernels need of every indenter.  Filled on the host for every force evaluation - the
-// geometry may be a formula of the step - and handed to the kernels by value, so a moving indenter costs no copy and no wait
-enum IndentKind { INDENT_SPHERE = 0, INDENT_CYLINDER = 1, INDENT_PLANE = 2 };
-struct IndentEntry {
-  int kind;                   // IndentKind
-  int axis;                   // cylinder: its axis; plane: its normal (0 x, 1 y, 2 z)
-  int side;                   // sphere | cylinder: side in (1) | out (0); plane: planeside, lo (-1) | hi (+1)
-  int groupbit;               // the fix's group (1 = all)
-  int phase;                  // 0: before fix langevin or without one, 1: behind it
-  int pad;
-  double k, k3;               // K and K / 3
-  double ctr[3];              // sphere | cylinder: the centre, remapped into the box as Domain::remap does
-  double r;                   // sphere | cylinder: the radius; plane: its position
-};
-struct IndentTable {
-  int n;
-  int pad;
-  IndentEntry e[INDENT_MAX];
-};
-constexpr int INDENT_COLS = 4;     // sums per entry: energy, force on the indenter x y z
-
-// fix spring/self | addforce | setforce (src/fix_spring_self.cpp, fix_addforce.cpp, fix_setforce.cpp): the post-force fixes that
-// act on chosen beads from outside, in the order the fixes were defined; built on the host at every `run`
-enum ForceOpKind { FORCEOP_SPRING = 0, FORCEOP_ADD = 1, FORCEOP_SET = 2 };
-struct ForceOpEntry {
-  int kind;                   // ForceOpKind
-  int groupbit;               // the fix's group (1 = all)
-  int phase;                  // 0: before fix langevin or without one, 1: behind it
-  int every;                  // addforce `every N`: acts on steps with ntimestep % N == 0 (the host states it per launch)
-  int mask;                   // bit c: spring/self has a spring along c | setforce sets component c (addforce: 7)
-  int pad;
-  double k;                   // spring/self: the spring constant
-  double v[3];                // addforce | setforce: the three values
-  const double *origin;       // spring/self: [3][stride] unwrapped origins by tag, device memory (members only are read)
-};
-struct ForceOpTable {
-  int n;
-  int stride;                 // natoms + 1: the row length of every origin block
-  ForceOpEntry e[FORCEOP_MAX];
-};
-constexpr int FORCEOP_COLS = 10;   // sums per entry: energy, foriginal x y z, virial xx yy zz xy xz yz
 
 struct DeviceState;  // defined in device.h (HIP side)
 struct Comm;         // defined in comm.h
@@ -411,7 +348,6 @@ class Engine {
   // says so, until someone who reads the table (Engine::pair_rows) or the end of the run asks for it
   void push_pair_table(bool mid_run);
   bool pair_table_stale = false;
-  long steps_fused_soft = 0;        // of steps_fused: the step kernel's soft variant
   long pair_table_copies = 0;       // mid-run copies of the pair table by fix adapt (lammps_le_stat "pair_table_copies")
   std::string pair_sig;             // pair style and neighbor cutoff of the last upload
   bool in_run = false;              // Update::whichflag != 0: ramp() is legal
@@ -457,8 +393,8 @@ class Engine {
   std::string thermo_float_format;     // thermo_modify format float: a checked printf conversion ("": %12.8g)
   bool want_fnorm = false;            // fmax or fnorm was named: thermo steps also reduce the force norms
   void print_thermo_header();
-  // what `run` and `minimize` do between init() and their setup: upload or refresh of the device state, the tables of the
-  // walls and force fixes, the modes of this run
+  // what `run` and `minimize` do between init() and their setup: the tables of the post-force fixes (first: what they refuse
+  // needs no device), upload or refresh of the device state, the modes of this run
   void begin_run_state();
   // ---- minimize (minimize.cpp; src/minimize.cpp, min.cpp, min_linesearch.cpp, min_cg.cpp, min_sd.cpp) ----
   std::string min_style = "cg";        // (src/update.cpp:60-62: cg without the command)
@@ -491,29 +427,18 @@ class Engine {
   double loop_time = 0.0;
   long neigh_builds = 0, neigh_dangerous = 0;
   long lazy_rebuilds = 0;      // rebuilds of this run that left the velocities to the step kernel (RB_LAZY_V), lammps_le_stat("lazy_rebuilds")
-  // time steps of the current run by the path they took (lammps_le_stat): the step kernel (of which: its group variant), the
+  // time steps of the current run by the path they took (lammps_le_stat "steps_*"): the step kernel - of which its group, wall,
+  // soft and EXT (spring/self, addforce, setforce inside the kernel) variants and the launches that carried an indenter -, the
   // step kernel's energy variant on a thermo step, the unfused kernels
-  long steps_fused = 0, steps_fused_group = 0, steps_fused_thermo = 0, steps_unfused = 0;
-  long steps_fused_wall = 0;   // of steps_fused: the step kernel's wall variant (fix wall/region inside the kernel)
-  // fix wall/region: the table of this run's walls (fix order), the fixes behind its rows
-  WallTable walltab{};
-  std::vector<FixWallRegion *> wall_fixes;
-  void build_wall_table();            // at every run (init() has checked the regions); emptied when the set of fixes changes
-  void wall_post_force(int phase, bool eflag);   // k_wall, k_indent, k_fixforce for the fixes before (0) / behind (1) fix langevin
-  // fix indent: the fixes of this run (fix order) and their place relative to fix langevin; the table of one force evaluation
-  std::vector<FixIndent *> indent_fixes;
-  std::vector<int> indent_phase;
-  long steps_fused_indent = 0;        // of steps_fused: the launch carried an indenter (lammps_le_stat "steps_fused_indent")
-  void build_indent_list();           // at every run, beside build_wall_table()
-  IndentTable indent_table();         // the geometry of step `ntimestep`: formulas evaluated on the host, centres remapped
-  IndentTable indent_now{};           // ... of the force evaluation under way
-  // fix spring/self | addforce | setforce: the table of this run (fix order), the fixes behind its rows
-  ForceOpTable forceoptab{};
-  std::vector<FixForceOp *> forceop_fixes;
-  long steps_fused_ext = 0;           // of steps_fused: the step kernel's EXT variant (these fixes inside the kernel)
-  void build_forceop_table();         // at every run, beside build_wall_table(); checks the order against the walls
-  unsigned forceop_active() const;    // bit k: entry k acts on step ntimestep (addforce `every`)
-  void forceop_post_force(int phase, bool eflag);   // k_fixforce for the entries of one phase, behind that phase's walls
+  struct StepCounters {
+    long fused = 0, fused_group = 0, fused_wall = 0, fused_soft = 0, fused_ext = 0, fused_indent = 0, fused_thermo = 0, unfused = 0;
+    void reset() { *this = StepCounters(); }
+  } steps;
+  // fix wall/region, fix indent, fix spring/self | addforce | setforce: the tables of this run, built by begin_run_state() (post_force.h)
+  PostForce postforce;
+  // the post-force fixes of phase 0, fix langevin if there is one (`fuse_final`: with the final half-kick in its kernel), the
+  // post-force fixes of phase 1 - the order of Modify::post_force, the same for every integrator and the minimiser
+  void post_force_sequence(FixLangevin *lg, bool eflag, bool fuse_final);
   StepKnobs step_knobs;        // the step kernel's environment switches as they stood when the current run began
   RebuildKnobs rebuild_knobs;  // ... and the rebuild's
   unsigned rebuild_plan_bits = 0;   // the plan the last rebuild (or regrow pass) executed, lammps_le_stat("rebuild_plan_full")

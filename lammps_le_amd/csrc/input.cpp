@@ -616,17 +616,13 @@ void Engine::execute(const std::string &cmd, std::vector<std::string> &arg) {
     else throw LammpsError("Unknown fix style " + st);
     apply_restart_state(f.get());     // a fix re-specified after read_restart continues its RNG stream (Fix::restart)
     fixes.push_back(std::move(f));
-    walltab.n = 0; wall_fixes.clear();      // (the next run builds the table of its walls)
-    forceoptab.n = 0; forceop_fixes.clear();
-    indent_fixes.clear(); indent_phase.clear();
+    postforce.clear();      // (the next run builds the tables of its post-force fixes)
   } else if (cmd == "unfix") {
     need(1);
     auto it = std::find_if(fixes.begin(), fixes.end(), [&](const std::unique_ptr<Fix> &f) { return f->id == arg[0]; });
     if (it == fixes.end()) throw LammpsError("Could not find fix ID to delete");
     fixes.erase(it);
-    walltab.n = 0; wall_fixes.clear();
-    forceoptab.n = 0; forceop_fixes.clear();
-    indent_fixes.clear(); indent_phase.clear();
+    postforce.clear();
   } else if (cmd == "fix_modify") {
     // src/modify.cpp:1052-1066 modify_fix, src/fix.cpp:134-176 modify_params: energy / virial for a fix that has them
     if (arg.size() < 2) throw LammpsError("Illegal fix_modify command");

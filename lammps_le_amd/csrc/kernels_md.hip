@@ -1778,16 +1778,17 @@ void launch_wall(DeviceState &d, const WallTable &wt, int phase, bool eflag) {
                        d.walltab_dev, phase, d.f[0], d.f[1], d.f[2], d.wall_partial, d.nred_blocks + 1, d.flags);
   }, eflag);
 }
-void reduce_wall_partials(DeviceState &d, const WallTable &wt, double *out) {
+// the totals of n rows of block sums of one family (wall_partial | forceop_partial | indent_partial): rows of 16 into out
+void reduce_rows(DeviceState &d, double *partial, int n, double *out) {
   const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
   const size_t rows = (size_t)d.nred_blocks + 1;
-  for (int k = 0; k < wt.n; k++) {
-    double *tab = d.wall_partial + (size_t)k * rows * 16;
+  for (int k = 0; k < n; k++) {
+    double *tab = partial + (size_t)k * rows * 16;
     hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
     HIP_CHECK(hipMemcpyAsync(d.partial_h + 16 * (size_t)k, tab + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
   }
   stream_sync(d);
-  for (int k = 0; k < 16 * wt.n; k++) out[k] = d.partial_h[k];
+  for (int k = 0; k < 16 * n; k++) out[k] = d.partial_h[k];
 }
 
 // fix indent: the rows of block sums (the table itself travels with every launch)
@@ -1810,18 +1811,6 @@ void launch_indent(DeviceState &d, const IndentTable &it, int phase, bool eflag)
                        it, d.box, phase, d.f[0], d.f[1], d.f[2], d.indent_partial, d.nred_blocks + 1);
   }, eflag);
 }
-void reduce_indent_partials(DeviceState &d, int nindent, double *out) {
-  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
-  const size_t rows = (size_t)d.nred_blocks + 1;
-  for (int k = 0; k < nindent; k++) {
-    double *tab = d.indent_partial + (size_t)k * rows * 16;
-    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
-    HIP_CHECK(hipMemcpyAsync(d.partial_h + 16 * (size_t)k, tab + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-  }
-  stream_sync(d);
-  for (int k = 0; k < 16 * nindent; k++) out[k] = d.partial_h[k];
-}
-
 void upload_forceop_table(DeviceState &d, ForceOpTable &ft, const double *const *origins, int natoms) {
   const size_t stride = (size_t)natoms + 1;
   ft.stride = (int)stride;
@@ -1871,20 +1860,8 @@ void launch_fixforce(DeviceState &d, const ForceOpTable &ft, int phase, unsigned
                        d.f[0], d.f[1], d.f[2], d.forceop_partial, d.nred_blocks + 1);
   }, eflag);
 }
-void reduce_fixforce_partials(DeviceState &d, const ForceOpTable &ft, double *out) {
-  const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
-  const size_t rows = (size_t)d.nred_blocks + 1;
-  for (int k = 0; k < ft.n; k++) {
-    double *tab = d.forceop_partial + (size_t)k * rows * 16;
-    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
-    HIP_CHECK(hipMemcpyAsync(d.partial_h + 16 * (size_t)k, tab + (size_t)nb * 16, 16 * sizeof(double), hipMemcpyDeviceToHost, d.stream));
-  }
-  stream_sync(d);
-  for (int k = 0; k < 16 * ft.n; k++) out[k] = d.partial_h[k];
-}
-
 // every sum of a thermo evaluation added up where it lies: the same k_colsum launches as the reduce_* functions above, no copy
-void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable &ft, int nindent, bool angles, MinSources &src) {
+void enqueue_thermo_sums(DeviceState &d, const PostForce &pf, bool angles, MinSources &src) {
   const int nb = std::max(1, (d.n + BLOCK - 1) / BLOCK);
   const size_t rows = (size_t)d.nred_blocks + 1;
   hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, (d.n + BLOCK - 1) / BLOCK, d.partial, d.partial + (size_t)((d.n + BLOCK - 1) / BLOCK) * 16);
@@ -1893,21 +1870,16 @@ void enqueue_thermo_sums(DeviceState &d, const WallTable &wt, const ForceOpTable
     hipLaunchKernelGGL((k_colsum<8>), dim3(1), dim3(BLOCK), 0, d.stream, nb, d.partial_a, d.partial_a + (size_t)nb * 8);
     src.add(d.partial_a + (size_t)nb * 8, 8);
   }
-  for (int k = 0; k < wt.n; k++) {
-    double *tab = d.wall_partial + (size_t)k * rows * 16;
-    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
-    src.add(tab + (size_t)nb * 16, 16);
-  }
-  for (int k = 0; k < ft.n; k++) {
-    double *tab = d.forceop_partial + (size_t)k * rows * 16;
-    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
-    src.add(tab + (size_t)nb * 16, 16);
-  }
-  for (int k = 0; k < nindent; k++) {      // (the four columns of an indenter)
-    double *tab = d.indent_partial + (size_t)k * rows * 16;
-    hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
-    src.add(tab + (size_t)nb * 16, INDENT_COLS);
-  }
+  auto family = [&](double *partial, int n, int cols) {
+    for (int k = 0; k < n; k++) {
+      double *tab = partial + (size_t)k * rows * 16;
+      hipLaunchKernelGGL((k_colsum<16>), dim3(1), dim3(BLOCK), 0, d.stream, nb, tab, tab + (size_t)nb * 16);
+      src.add(tab + (size_t)nb * 16, cols);
+    }
+  };
+  family(d.wall_partial, pf.walltab.n, 16);
+  family(d.forceop_partial, pf.forceoptab.n, 16);
+  family(d.indent_partial, (int)pf.indent_fixes.size(), INDENT_COLS);      // (the four columns of an indenter)
 }
 
 // sum the per-block partials in a fixed order (deterministic); the totals land in the table's spare row nb

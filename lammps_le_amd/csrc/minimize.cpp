@@ -58,8 +58,7 @@ struct Minimizer {
   // forces, energies, the fixes with a min_post_force hook, the dots: enqueue, wait once, read the record
   void evaluate(bool with_ke) {
     e.compute_forces(true);
-    e.wall_post_force(0, true);       // FixWallRegion | FixSpringSelf | FixAddForce | FixSetForce::min_post_force, in fix order
-    e.wall_post_force(1, true);
+    e.post_force_sequence(nullptr, true, false);      // FixWallRegion | FixIndent | FixSpringSelf | FixAddForce | FixSetForce::min_post_force, in fix order; no thermostat
     if (with_ke) {
       TypeTables tt{};
       for (int t = 1; t <= e.ntypes; t++) tt.mass[t] = e.mass[t];
@@ -68,22 +67,17 @@ struct Minimizer {
     launch_min_dots(d, cg, true);
     MinSources src;
     const bool ang = e.angles_active();
-    const int nind = (int)e.indent_fixes.size();
-    enqueue_thermo_sums(d, e.walltab, e.forceoptab, nind, ang, src);
+    enqueue_thermo_sums(d, e.postforce, ang, src);
     launch_min_collect(d, true, src);
     wait();
     const double *rec = d.min_rec;
     ff = rec[MIN_FF]; fh = rec[MIN_FH]; fg = rec[MIN_FG]; fmax2 = rec[MIN_FMAX2]; fmaxc = rec[MIN_FMAXC];
-    double s[16 + 16 * WALL_MAX + 16 * FORCEOP_MAX + 16 * INDENT_MAX], a8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double s[PostForce::SUMS_MAX], a8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const double *p = rec + MIN_DOT_COLS;
     for (int k = 0; k < 16; k++) s[k] = p[k];
     p += 16;
     if (ang) { for (int k = 0; k < 8; k++) a8[k] = p[k]; p += 8; }
-    const int nrest = 16 * (e.walltab.n + e.forceoptab.n);
-    for (int k = 0; k < nrest; k++) s[16 + k] = p[k];
-    p += nrest;
-    for (int k = 0; k < nind; k++)      // (the record holds the four columns of an indenter, thermo_from_sums reads rows of 16)
-      for (int c = 0; c < 16; c++) s[16 + nrest + 16 * k + c] = c < INDENT_COLS ? p[INDENT_COLS * k + c] : 0.0;
+    e.postforce.unpack_min_record(p, s);
     if (with_ke) ke_sum = s[14];      // (the velocities do not change in a minimisation)
     s[14] = ke_sum;
     row = e.thermo_from_sums(s, ang ? a8 : nullptr, e.want_ptensor ? k6 : nullptr);
@@ -310,7 +304,6 @@ void Engine::minimize(double etol, double ftol, long maxiter, long maxeval) {
   for (int a = 1; a <= nangletypes && apa > 0 && nangles > 0 && !angle_style_name.empty() && angle_style_name != "none" && angle_style_name != "zero"; a++)
     if (!angtab.style[a]) throw LammpsError("All angle coeffs are not set");
   init();
-  build_forceop_table();
   begin_run_state();
   beginstep = ntimestep;
   endstep = ntimestep + maxiter;
@@ -341,7 +334,7 @@ void Engine::minimize(double etol, double ftol, long maxiter, long maxeval) {
   reneighbor(false, sortfreq > 0);
   neigh_builds = 0;
   lazy_rebuilds = 0;
-  steps_fused = steps_fused_group = steps_fused_thermo = steps_unfused = steps_fused_wall = steps_fused_soft = steps_fused_ext = steps_fused_indent = 0;
+  steps.reset();
   if (want_ptensor) {
     TypeTables tt{};
     for (int t = 1; t <= ntypes; t++) tt.mass[t] = mass[t];

@@ -164,7 +164,10 @@ class PrunedSoft(Pruned, sr.SoftSystem):
 
 
 def _trajectory(family, langevin):
-    """One run of the restatement in the precision in force (force_reference.precision)."""
+    """One run of the restatement in the precision in force (force_reference.precision).  family "together": the families in
+    one run, `langevin` = the run style ("verlet" | "respa")."""
+    if family == "together":
+        return _together(langevin)
     from oracle import ranmars_stream
     s = system()
     model = fr.model_from_script(script("nopair" if family == "soft" else family, langevin), s["ntypes"])
@@ -200,6 +203,214 @@ def _trajectory(family, langevin):
     return S, tr
 
 
+# ------------------------------------------------------------------------------------------------------------------
+# The post-force families together (test_gpu_postforce_together.py): the wall, a tether on a group and a pull with `every 3`
+# ahead of fix langevin, the indenter and a pinned group behind it, through the three callers of the engine's post-force
+# sequence.  Under run_style respa the engine refuses fix setforce (FixForceOp::init): that run goes without the pinned group.
+# The minimiser ignores the thermostat; its line stays in the script, so the indenter and the pinned group keep their place.
+MODES = ("verlet", "respa", "minimize")
+TETHERED, PINNED = (200, 900), (40, 47)          # ranges of IDs, both ends included
+PIN = (0.0, None, 0.25)
+PULL_EVERY = 3
+RESPA_INNER = 2
+FIX_COLUMNS = {"w": 3, "s": 0, "a": 3, "c": 3, "z": -3}          # fix ID -> length of its vector (negative: it has no scalar)
+
+
+def fix_columns(mode):
+    """The f_ID / f_ID[k] thermo columns of the run's fixes, in fix order."""
+    out = []
+    for fid, nvec in FIX_COLUMNS.items():
+        if fid == "z" and mode == "respa":
+            continue
+        out += ["f_" + fid] * (nvec >= 0) + ["f_%s[%d]" % (fid, k + 1) for k in range(abs(nvec))]
+    return out
+
+
+def together_script(mode, log=None):
+    ff, wall = family_lines("wall")
+    _, indent = family_lines("indent")
+    text = fi.script(dict(fi.INPUTS[NAME](), force_field=ff), skin=repr(SKIN))
+    text += "group teth id <> %d %d\ngroup pin id <> %d %d\n" % (TETHERED + PINNED)
+    text += "fix 1 all nve\n" + wall + "fix s teth spring/self %.17g\n" % TETHER_K
+    text += "fix a all addforce %.17g %.17g %.17g every %d\n" % (PULL + (PULL_EVERY,)) + LANGEVIN + indent
+    if mode != "respa":
+        text += "fix z pin setforce %s\n" % " ".join("NULL" if c is None else repr(c) for c in PIN)
+    text += "fix_modify w energy yes\nfix_modify c energy yes\nfix_modify a energy yes\n"
+    text += "thermo_style custom step temp epair emol etotal press pe %s\nthermo_modify format float %%.17g\n" % " ".join(fix_columns(mode))
+    text += "thermo %d\n" % THERMO + ("log %s\n" % log if log else "")
+    if mode == "respa":
+        text += "run_style respa 2 %d\n" % RESPA_INNER
+    return text + ("minimize 0.0 0.0 %d 1000\n" % fc.STEPS if mode == "minimize" else "run %d\n" % fc.STEPS)
+
+
+class Together:
+    """The five fixes on the forces of one evaluation, in fix order: ahead() of the thermostat, behind() it.  efix = what
+    `fix_modify energy yes` adds to pe at the last evaluation (an addforce that skipped it keeps what it last reported)."""
+
+    def __init__(self, s, x0, img0, pinned=True):
+        n = len(x0)
+        self.box, self.pinned = s["box"], pinned
+        self.teth = er.members(n, range(TETHERED[0], TETHERED[1] + 1))
+        self.pin = er.members(n, range(PINNED[0], PINNED[1] + 1))
+        self.ahead_fixes = [er.spring(TETHER_K, self.teth, er.unwrapped(x0, img0, s["box"])), er.add(PULL, np.ones(n, dtype=bool), every=PULL_EVERY)]
+        self.e = dict(w=0, a=0, c=0)
+        self.acting = dict(w=0, c=0, z=0.0)
+
+    def ahead(self, step, x, img, f):
+        t = wr.wall_terms(x, wall_region(), WALL)
+        assert not t["outside"].any(), "a bead inside the ball"
+        self.acting["w"] = max(self.acting["w"], int((t["ncontact"] > 0).sum()))
+        f, out = er.apply(self.ahead_fixes, x, img, self.box, f + t["f"], step)
+        self.e["w"] = t["energy"]
+        if out[1] is not None:
+            self.e["a"] = out[1]["energy"]
+        return f
+
+    def behind(self, step, x, img, f):
+        t = ir.terms(x, indenter(), self.box)
+        self.acting["c"] = max(self.acting["c"], int(t["touched"].sum()))
+        self.e["c"] = t["energy"]
+        f = f + t["f"]
+        if self.pinned:
+            before = f
+            f, _ = er.apply([er.setforce(PIN, self.pin)], x, img, self.box, f, step)
+            self.acting["z"] = max(self.acting["z"], float(np.abs(fr.ld(f) - fr.ld(before)).max()))
+        return f
+
+    def efix(self):
+        return self.e["w"] + self.e["a"] + self.e["c"]
+
+
+def respa_trajectory(S, x0, v0, img0, nsteps, uniforms, ahead, behind, inner=RESPA_INNER):
+    """force_reference.System.trajectory under `run_style respa 2 inner`: the bonds on the inner level with timestep dt / inner,
+    the pair term, the post-force fixes and the thermostat on the outer one (Respa::recurse: the outer half-kick, `inner` inner
+    velocity-Verlet steps, the outer forces at the positions those leave and with the velocities of that moment, the outer
+    half-kick).  f = the sum of the levels, as the engine holds it after a step with a thermo row."""
+    x, v, img = fr.ld(x0).copy(), fr.ld(v0).copy(), np.asarray(img0, dtype=np.int64).copy()
+    dt = fr.LD(S.model.dt)
+    dti = dt / inner
+    half_o = (dt / 2 * fr.LD(S.units["ftm2v"]) / S.m)[:, None]
+    half_i = (dti / 2 * fr.LD(S.units["ftm2v"]) / S.m)[:, None]
+    n3 = 3 * S.n
+
+    def outer(step, ev):
+        f = ahead(step, x, img, ev.f_pair)
+        return behind(step, x, img, f + S.langevin_force(v, uniforms[step * n3:(step + 1) * n3]))
+    ev = S.evaluate(x)
+    f0, f1 = ev.f_bond, outer(0, ev)
+    xs, vs, rows, gaps, hooks = [], [], [], [], []
+    for step in range(nsteps + 1):
+        if step:
+            v = v + half_o * f1
+            for _ in range(inner):
+                v = v + half_i * f0
+                x = x + dti * v
+                S.wrap(x, img)
+                ev = S.evaluate(x)
+                f0 = ev.f_bond
+                v = v + half_i * f0
+            f1 = outer(step, ev)
+            v = v + half_o * f1
+        xs.append(S.unwrapped(x, img)); vs.append(v.copy()); rows.append(S.thermo(ev, v)); gaps.append(ev.gap)
+    return dict(x=xs, v=vs, rows=rows, gaps=gaps, f=f0 + f1, xw=x, img=img, last=ev)
+
+
+def _together(mode):
+    from oracle import ranmars_stream
+    s = system()
+    S = PrunedSystem(fr.model_from_script(script("wall", True), s["ntypes"]), s["box"], s["type"], s["mass"], s["bonds"])
+    x0, img0 = wrap_into_box(s)
+    T = Together(s, x0, img0, pinned=mode != "respa")
+    efix = {}
+
+    def behind(step, x, img, f):
+        f = T.behind(step, x, img, f)
+        efix[step] = T.efix()
+        return f
+    u = ranmars_stream(fc.LANGEVIN_SEED, 3 * S.n * (fc.STEPS + 1))
+    if mode == "respa":
+        tr = respa_trajectory(S, x0, s["v"], img0, fc.STEPS, u, T.ahead, behind)
+    else:
+        tr = S.trajectory(x0, s["v"], img0, fc.STEPS, u, extra=T.ahead, after=behind)
+    for k, r in enumerate(tr["rows"]):          # (fix_modify energy yes on the wall, the pull and the indenter)
+        r["etotal"] = r["etotal"] + efix[k] / fr.LD(S.n)
+    tr["acting"] = T.acting
+    return S, tr
+
+
+TOGETHER_STATS = ("neigh_builds", "steps_fused", "steps_fused_thermo", "steps_unfused", "min_iterations", "min_evals")
+
+
+def run_together(mode, tmp_path):
+    """The run on the engine -> x, v, f, image by ID, thermo_history(), `log`: the printed thermo rows with %.17g (what the
+    engine's doubles are, digit for digit), the step counters."""
+    import os
+    from systems import run_product
+    log = os.path.join(str(tmp_path), "log.together")
+    p = run_product(together_script(mode, log), system(), tmp_path)
+    try:
+        got = dict(x=p.gather("x"), v=p.gather("v"), image=p.gather("image"), f=p.gather("f"), rows=np.asarray(p.thermo_history()),
+                   stats={k: int(p.stat(k)) for k in TOGETHER_STATS}, pe=p.get_thermo("pe"))
+        got["builds"] = got["stats"]["neigh_builds"]
+        p.command("log none")
+    finally:
+        p.close()
+    ncol = 7 + len(fix_columns(mode))
+    rows = []
+    for ln in open(log):
+        w = ln.split()
+        if len(w) == ncol and w[0].isdigit():
+            rows.append([float(v) for v in w])
+    got["log"] = np.array(rows)
+    return got
+
+
+SAMPLE_EVERY = 16
+
+
+def sample_beads(n):
+    """The beads whose end state a record holds value by value: every sixteenth and the pinned group (indices, ID - 1)."""
+    return np.array(sorted(set(range(0, n, SAMPLE_EVERY)) | set(range(PINNED[0] - 1, PINNED[1]))))
+
+
+def digest(a, dtype=np.float64):
+    """SHA-256 of an array's values as little-endian `dtype` in C order: equal exactly when every element is, bit for bit."""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a, dtype=np.dtype(dtype).newbyteorder("<")).tobytes()).hexdigest()
+
+
+def together_pack(mode, got):
+    """What tests/golden/postforce_together_<mode>.json holds of a run: the thermo rows and printed columns as hex floats, the
+    step counters, the end state of ALL beads as the SHA-256 of positions, velocities and image flags (a record of every
+    double of three runs is a megabyte of text) and of sample_beads() value by value as hex floats."""
+    k = sample_beads(len(got["x"]))
+    hexed = lambda a: [[float(v).hex() for v in row] for row in np.atleast_2d(a)]
+    return dict(mode=mode, steps=fc.STEPS, thermo=THERMO, columns=["step", "temp", "epair", "emol", "etotal", "press", "pe"] + fix_columns(mode),
+                stats=got["stats"], rows=hexed(got["rows"]), log=hexed(got["log"]),
+                sha256=dict(x=digest(got["x"]), v=digest(got["v"]), image=digest(got["image"], np.int64)),
+                sample=dict(beads=k.tolist(), x=hexed(got["x"][k]), v=hexed(got["v"][k]), image=np.asarray(got["image"])[k].tolist()))
+
+
+def write_record(rec, path):
+    """together_pack's dict as JSON with one key of the record and of its sample per line."""
+    import json
+    line = lambda d: ",\n".join("%s:%s" % (json.dumps(k), json.dumps(d[k], separators=(",", ":"))) for k in sorted(d) if k != "sample")
+    with open(path, "w") as fh:
+        fh.write("{" + line(rec) + ',\n"sample":{\n' + line(rec["sample"]) + "}}\n")
+
+
+def together_record(mode):
+    """tests/golden/postforce_together_<mode>.json: what the commit before the post-force fixes got one owner left on an MI355X
+    (make_postforce_together.py, together_pack)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "postforce_together_%s.json" % mode)) as fh:
+        z = json.load(fh)
+    unhex = lambda rows: np.array([[float.fromhex(v) for v in r] for r in rows])
+    s = z["sample"]
+    return dict(z, rows=unhex(z["rows"]), log=unhex(z["log"]), sample=dict(beads=np.array(s["beads"]), x=unhex(s["x"]), v=unhex(s["v"]), image=np.array(s["image"])))
+
+
 def list_builds(xs):
     """The displacement rule of the reference trajectory itself (neigh_modify every 1 delay 1 check yes): a build at every step
     on which some bead is farther than half the skin from where it was at the last build.  -> (steps with a build, the
@@ -227,13 +438,9 @@ def image_flags(S, xs, builds):
     return img.astype(np.int64), float((np.minimum(off, 1 - off) * S.prd).min())
 
 
-@functools.lru_cache(maxsize=None)
-def reference(family, langevin):
-    """(system, long-double trajectory, {x, v, f, rows: deviation of the float64 run of the same restatement}, steps with a
-    list build)"""
-    S, ref = _trajectory(family, langevin)
-    with fr.precision(np.float64):
-        _, low = _trajectory(family, langevin)
+def _deviation(ref, low):
+    """({x, v, f, rows: deviation of the float64 run `low` of a restatement from its long-double run `ref`}, steps with a list
+    build)"""
     assert low["x"][-1].dtype == np.float64 and low["f"].dtype == np.float64 and ref["x"][-1].dtype == fr.LD
     dev = dict(x=fc.relerr(low["x"][-1], ref["x"][-1]), v=fc.relerr(low["v"][-1], ref["v"][-1]), f=fc.relerr(low["f"], ref["f"]),
                rows=max(fc.relerr(low["rows"][k][key], ref["rows"][k][key]) for k in range(fc.STEPS + 1) for key in fc.ROW_KEYS))
@@ -242,7 +449,17 @@ def reference(family, langevin):
     assert moved < REACH / 2, moved
     builds, margin = list_builds(ref["x"])
     assert margin > 1e-6, margin          # (no step's largest displacement is at the trigger)
-    return S, ref, dev, builds
+    return dev, builds
+
+
+@functools.lru_cache(maxsize=None)
+def reference(family, langevin):
+    """(system, long-double trajectory, {x, v, f, rows: deviation of the float64 run of the same restatement}, steps with a
+    list build)"""
+    S, ref = _trajectory(family, langevin)
+    with fr.precision(np.float64):
+        _, low = _trajectory(family, langevin)
+    return (S, ref) + _deviation(ref, low)
 
 
 def required_gap(S, dev):

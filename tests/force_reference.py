@@ -450,7 +450,7 @@ class System:
     def unwrapped(self, x, img):
         return ld(x) + ld(img) * self.prd
 
-    def trajectory(self, x0, v0, img0, nsteps, uniforms=None, topology=None, extra=None):
+    def trajectory(self, x0, v0, img0, nsteps, uniforms=None, topology=None, extra=None, after=None):
         """Velocity Verlet from the state read_data leaves (x0 inside the box, image flags img0): setup, then nsteps steps.
         Returns per step (0 .. nsteps) the unwrapped positions, velocities, thermo rows and min |r^2 - cut^2|, and the
         force array of the last step (with the Langevin force, as the engine's f holds it).
@@ -460,7 +460,9 @@ class System:
         extra(step, x, img, f) -> f: the hook for force terms of other modules (a wall, an indenter, a tether, a pull) - it takes
         the positions inside the box, the image flags and the force of the model's own terms at the evaluation of `step` and
         returns the force with its terms added, before the thermostat's.  The thermo rows stay the model's own (a fix enters
-        them only under fix_modify)."""
+        them only under fix_modify).
+        after(step, x, img, f) -> f: the same for the terms of fixes defined behind the thermostat - it takes the force with the
+        thermostat's in it (a fix setforce there overwrites that too)."""
         assert self.model.nve
         x, v, img = ld(x0).copy(), ld(v0).copy(), np.asarray(img0, dtype=np.int64).copy()
         dt = LD(self.model.dt)
@@ -483,6 +485,8 @@ class System:
             f = ev.f if extra is None else extra(step, x, img, ev.f)
             if self.model.langevin:
                 f = f + self.langevin_force(v, uniforms[step * n3:(step + 1) * n3])
+            if after is not None:
+                f = after(step, x, img, f)
             return ev, f
 
         ev, f = forces(0)
