@@ -333,6 +333,16 @@ static void scatter_subset_impl(Engine *e, const char *fn, const char *name, int
   const bool typ = type == 0 && count == 1 && k == "type";
   if (!dbl3 && !img && !typ) throw LammpsError(std::string(fn) + ": unknown property name " + k);
   check_ids(e, fn, ndata, ids);
+  // a type outside 1 .. ntypes: the reference writes it and fails later in its pair style; here it would index the per-type
+  // tables out of range on the device, so it is refused before anything is written, on the host copies and on the device alike
+  // (every row sent is read, ahead of the last-row-wins of a repeated ID: an invalid row that a later valid one would have
+  // overwritten is refused too, where the reference would end with the valid value - stricter, never less safe)
+  if (typ)
+    for (int r = 0; r < ndata; r++) {
+      const int t = ((const int *)data)[r];
+      if (t < 1 || t > e->ntypes)
+        throw LammpsError(std::string(fn) + ": invalid atom type " + std::to_string(t) + " for atom ID " + std::to_string(ids[r]));
+    }
   // a repeated ID takes its last row, as the reference's sequential loop leaves it
   const size_t rowb = (size_t)count * (dbl3 ? sizeof(double) : sizeof(int));
   std::vector<int> uid;
@@ -894,6 +904,7 @@ double lammps_le_stat(void *handle, const char *name) {
   if (k == "pair_rows_count_ms") return e->pair_rows_ms[0];            // ... its count pass + scan, its fill pass + copy (host wall clock)
   if (k == "pair_rows_fill_ms") return e->pair_rows_ms[1];
   if (k == "host_downloads") return (double)e->host_downloads;          // whole-system downloads (Engine::download)
+  if (k == "device_current") return (e->dev && e->dev_current) ? 1.0 : 0.0;   // 0: the host copies are the state, the next run uploads
   if (k == "device_bytes") return e->dev ? (double)e->dev->mem.device_bytes() : 0.0;   // device blocks this handle holds
   if (k == "subset_comm_bytes") return e->subset_comm_bytes;           // this rank's share of the subset calls' collectives
   return -1.0;

@@ -89,9 +89,15 @@ __global__ __launch_bounds__(BLOCK) void k_dd_leave(int n, int nslots, int npad,
       // owner = slab index from one expression that every rank evaluates identically
       int owner = (int)((r.z - box.lo[2]) / width);
       owner = min(max(owner, 0), P - 1);
-      double zc = zrel_slab(r.z, slab_lo, box);      // direction of travel for a bead that left
-      godn = owner != me && zc < 0.0;
-      goup = owner != me && zc >= 0.0;
+      // a bead that left goes to the neighbour that owns it.  The sign of its offset from the bottom of my slab tells the
+      // direction only where it cannot tell apart the two: with two slabs (both neighbours are the other rank) - and for a
+      // bead no neighbour owns, which no step produces and capi.cpp keeps off this path.  With three slabs a bead a C-ABI
+      // scatter put into the upper half of the upper neighbour's slab is more than Lz / 2 above my bottom: by the sign it
+      // would travel down, to a rank that does not own it
+      const bool up = owner == (me + 1) % P, dn = owner == (me + P - 1) % P;
+      const bool by_sign = zrel_slab(r.z, slab_lo, box) >= 0.0;
+      goup = owner != me && (up != dn ? up : by_sign);
+      godn = owner != me && !goup;
     }
     gone[p] = (godn || goup) ? 1 : 0;
     // (active lanes are a prefix of the wavefront, as count_into_cell asks)

@@ -1873,6 +1873,9 @@ void leo_get_image(leo_t *s, int *o) { BYTAG(o, s->img, 3, int); }
 void leo_get_local_order(leo_t *s, int *o) { memcpy(o, s->tag, s->n * sizeof(int)); }
 void leo_set_x(leo_t *s, const double *x) { for (int i = 0; i < s->n; i++) memcpy(s->x + 3 * i, x + 3 * (size_t)(s->tag[i] - 1), 3 * sizeof(double)); }
 void leo_set_v(leo_t *s, const double *v) { for (int i = 0; i < s->n; i++) memcpy(s->v + 3 * i, v + 3 * (size_t)(s->tag[i] - 1), 3 * sizeof(double)); }
+/* the types by tag, as scatter_atoms_subset leaves them (src/library.cpp:2482-2614): every consumer - pair coefficients, masses, the
+   thermostat's per-type factors, the fixes' type tests - reads s->type[i] at its next use, nothing is derived ahead of it */
+void leo_set_type(leo_t *s, const int *t) { for (int i = 0; i < s->n; i++) s->type[i] = t[s->tag[i] - 1]; }
 void leo_get_bonds(leo_t *s, int *nb, int *bt, int *ba) {
   BYTAG(nb, s->num_bond, 1, int); BYTAG(bt, s->bond_type, s->bpa, int); BYTAG(ba, s->bond_atom, s->bpa, int);
 }

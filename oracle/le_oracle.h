@@ -141,6 +141,7 @@ void   leo_get_image(leo_t *s, int *out);
 void   leo_get_local_order(leo_t *s, int *out_tags);   /* tag of local index i */
 void   leo_set_x(leo_t *s, const double *x_by_tag);
 void   leo_set_v(leo_t *s, const double *v_by_tag);
+void   leo_set_type(leo_t *s, const int *type_by_tag);
 /* topology, tag order: num_bond[n], bond_type[n*bpa], bond_atom[n*bpa] */
 void   leo_get_bonds(leo_t *s, int *num_bond, int *bond_type, int *bond_atom);
 void   leo_get_special(leo_t *s, int *nspecial3, int *special);

@@ -297,6 +297,9 @@ class Oracle:
     def set_v(self, v):
         self.L.leo_set_v(self.h, _dp(np.ascontiguousarray(v, dtype=np.float64)))
 
+    def set_type(self, t):
+        self.L.leo_set_type(self.h, _ip(np.ascontiguousarray(t, dtype=np.int32)))
+
     def bond_table(self):
         bpa = self.L.leo_bond_per_atom(self.h)
         nb = np.zeros(self.n, dtype=np.int32)
