@@ -1144,7 +1144,7 @@ extern "C" void lammps_le_debug_le_array(void *handle, int slot, int n, int *out
 }
 
 // test hooks of the launch census (not part of the reference surface, not declared in include/lammps_le.h).  kernel: 0 = k_step
-// (keys: step_variant_key), 1 = k_force (force_variant_key), step_plan.h.
+// (keys: StepKeyBit, the template argument of k_step), 1 = k_force (force_variant_key), step_plan.h.
 // The launches of a handle so far as (key, count) pairs with count > 0, ascending by key; returns how many there are (at most
 // `cap` are stored)
 extern "C" int lammps_le_test_step_census(void *handle, int kernel, int cap, int *keys, long long *counts) {
@@ -1169,15 +1169,17 @@ extern "C" int lammps_le_test_step_keys(int kernel, int cap, int *keys) {
   const int space = kernel ? lmp_le::FORCE_KEY_SPACE : lmp_le::STEP_KEY_SPACE;
   int n = 0;
   for (int k = 0; k < space; k++)
-    if (kernel ? lmp_le::force_key_exists(k) : lmp_le::step_key_exists(k)) { if (n < cap) keys[n] = k; n++; }
+    if (kernel ? lmp_le::force_key_exists(k) : lmp_le::step_variant_exists(k)) { if (n < cap) keys[n] = k; n++; }
   return n;
 }
-// key -> the template arguments in the template's order (k_step: fifteen, LPB as 1 | 4; k_force: four) and back
+// key -> one number per bit, lowest first (k_step: fifteen, the lanes per bead of SK_LPB4 as 1 | 4; k_force: four) and back
 extern "C" void lammps_le_test_step_key_decode(int kernel, int key, int *flags) {
-  if (kernel) for (int b = 0; b < lmp_le::FORCE_KEY_BITS; b++) flags[b] = (key >> b) & 1;
-  else lmp_le::step_key_decode(key, flags);
+  for (int b = 0; b < (kernel ? lmp_le::FORCE_KEY_BITS : lmp_le::STEP_KEY_BITS); b++) flags[b] = (key >> b) & 1;
+  if (!kernel) flags[4] = (key & lmp_le::SK_LPB4) ? 4 : 1;
 }
 extern "C" int lammps_le_test_step_key(int kernel, const int *f) {
-  if (kernel) return lmp_le::force_variant_key(f[0], f[1], f[2], f[3]);
-  return lmp_le::step_variant_key(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14]);
+  int key = 0;
+  for (int b = 0; b < (kernel ? lmp_le::FORCE_KEY_BITS : lmp_le::STEP_KEY_BITS); b++) key |= (f[b] != 0) << b;
+  if (!kernel && f[4] != 4) key &= ~lmp_le::SK_LPB4;
+  return key;
 }

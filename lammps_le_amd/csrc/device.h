@@ -381,7 +381,7 @@ struct DeviceState {
   double *min_partial = nullptr;    // [blocks + 1][MIN_DOT_COLS]
   double *min_rec = nullptr;        // [MIN_REC_MAX] pinned, mapped
   double *min_rec_dev = nullptr;    // its device-side address (a view)
-  // ---- launch census: launches of k_step by step_variant_key and of k_force by force_variant_key (step_plan.h), host memory,
+  // ---- launch census: launches of k_step<KEY> by KEY and of k_force by force_variant_key (step_plan.h), host memory,
   // over the life of the handle (the diagnostic launch and the relaunch behind regrow_lists count); read by the test hooks
   // lammps_le_test_step_census* (capi.cpp) and written out by ~Engine under LAMMPS_LE_STEP_CENSUS_FILE ----
   unsigned step_census[STEP_KEY_SPACE] = {0};

@@ -910,7 +910,7 @@ __global__ __launch_bounds__(BLOCK) void k_force(ForceArgs A, BondTable bt, Box 
 // every fourth list entry and every fourth bond slot, the partial forces meet in a two-step butterfly and lane 0
 // integrates: the chain shrinks to one or two stages.
 // ANG: runs with an angle style - the angle forces of this step were written into fx / fy / fz by k_angle<.., OVERWRITE>
-// right before this launch and are added to the bead's sums (a template parameter, not a run-time test: the step kernel's
+// right before this launch and are added to the bead's sums (a bit of the kernel's key, not a run-time test: the step kernel's
 // schedule is sensitive - a pointer test here cost every run 2 us per launch)
 #define ANGLE_SMALL 0.001
 // the listed angles of one bead (records of k_angle_list): its own share of every one - f1 as atom 1, -(f1 + f3) as the
@@ -989,7 +989,7 @@ __device__ __forceinline__ void bead_angles(int p, const double4 &rp, int na, co
 // The parameters from `tag` on are the members of S and k_step's five direct pointers once more, __restrict__-qualified: the
 // loads of level 0 / level 1 below and of the AHEAD shapes move ahead of the stores into `flags` only with it (StepKernelArgs).
 // Read straight from S here, the members give 2 instantiations other VGPR counts and the wall variants vector loads of their table.
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP, bool LAZYV, bool WALL, bool SOFT, bool EXT, bool INDENT>
+template <int KEY>
 __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &bt, const Box &box, const TypeTables &tt, const StepKernelArgs &S,
                                           const double *s_tab, const double *s_bt,
                                           const int *__restrict__ tag, const int *__restrict__ crank,
@@ -1004,6 +1004,10 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
                                           const int *__restrict__ vperm, double *__restrict__ vxo,
                                           double *__restrict__ vyo, double *__restrict__ vzo,
                                           const WallTable *__restrict__ wt, const IndentTable &indents) {
+  constexpr bool LANGEVIN = KEY & SK_LANGEVIN, NEXT = KEY & SK_NEXT, IDENT = KEY & SK_IDENT, HAS_PAIR = KEY & SK_PAIR, DIAG = KEY & SK_DIAG,
+                 AHEAD = KEY & SK_AHEAD, ANG = KEY & SK_ANG, EF = KEY & SK_EF, GRP = KEY & SK_GRP, LAZYV = KEY & SK_LAZYV,
+                 WALL = KEY & SK_WALL, SOFT = KEY & SK_SOFT, EXT = KEY & SK_EXT, INDENT = KEY & SK_INDENT;
+  constexpr int LPB = (KEY & SK_LPB4) ? 4 : 1;      // lanes per bead
   int lb = logical_block(A.nblocks);
   const int sub = (LPB == 1) ? 0 : (int)(threadIdx.x % LPB);
   int p = lb * (BLOCK / LPB) + threadIdx.x / LPB;
@@ -1130,27 +1134,19 @@ __device__ __forceinline__ void step_body(const ForceArgs &A, const BondTable &b
   if (LAZYV) { vxo[p] = a; vyo[p] = b; vzo[p] = c; }
   else { vx[p] = a; vy[p] = b; vz[p] = c; }
 }
-template <bool LANGEVIN, bool NEXT, bool IDENT, bool HAS_PAIR, int LPB, bool DIAG, bool AHEAD, bool ANG = false, bool EF = false,
-          bool GRP = false, bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false>
-__global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
-                                                                                           StepKernelArgs S, double *__restrict__ fx,
-                                                                                           double *__restrict__ fy, double *__restrict__ fz,
-                                                                                           double4 *__restrict__ pos_next,
-                                                                                           const double4 *__restrict__ xhold) {
+// KEY: the instantiation, as the bits of step_plan.h (StepKeyBit) - a kernel trace shows k_step<1039>, and
+// `python tests/step_census.py 1039` says which flags that is
+template <int KEY>
+__global__ __launch_bounds__(BLOCK, ((KEY & (SK_AHEAD | SK_EF)) ? 1 : STEP_WAVES_PER_SIMD)) void k_step(ForceArgs A, BondTable bt, Box box, TypeTables tt,
+                                                                                                    StepKernelArgs S, double *__restrict__ fx,
+                                                                                                    double *__restrict__ fy, double *__restrict__ fz,
+                                                                                                    double4 *__restrict__ pos_next,
+                                                                                                    const double4 *__restrict__ xhold) {
   // (fx, fy, fz: stored by launches without NEXT, read first when ANG && !NEXT; why these five are not members: StepKernelArgs)
   static_assert(sizeof(ForceArgs) + sizeof(BondTable) + sizeof(Box) + sizeof(TypeTables) + sizeof(StepKernelArgs) <= 4096,
                 "the by-value arguments of k_step exceed the 4 KiB kernel-argument limit");
-  static_assert(!WALL || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD)),
-                "wall variant: the three plain shapes with a pair style");
-  static_assert(!SOFT || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && (LPB == 1 || AHEAD)),
-                "soft variant: the three plain shapes with a pair style");
-  static_assert(!EXT || (HAS_PAIR && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && !SOFT && (LPB == 1 || AHEAD)),
-                "EXT variant: the three plain shapes with a pair style");
-  static_assert(!INDENT || (WALL && !SOFT && !EXT), "indent variant: a wall variant that also takes the launch's indenters");
-  static_assert(!LAZYV || (NEXT && HAS_PAIR && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP),
-                "velocity hand-over: the throughput shape only");
-  static_assert(!EF || (!NEXT && LPB == 1), "energy variant: NEXT = false, one lane per bead");
-  static_assert(!GRP || (!IDENT && !EF && !AHEAD && LPB == 1), "group variant: plain shape, ranks from a table");
+  static_assert(step_variant_exists(KEY), "no such variant of the step kernel (step_plan.h)");
+  constexpr bool EF = KEY & SK_EF, HAS_PAIR = KEY & SK_PAIR;
   __shared__ double s_tab[6 * (MAXTYPES + 1) * (MAXTYPES + 1)];
   __shared__ double s_bt[(MAXTYPES + 1) * BT_W];
   fill_bond_table(bt, s_bt);
@@ -1163,7 +1159,7 @@ __global__ __launch_bounds__(BLOCK, ((AHEAD || EF) ? 1 : STEP_WAVES_PER_SIMD)) v
 #pragma unroll
     for (int k = 0; k < 14; k++) e[k] = 0.0;
   }
-  step_body<LANGEVIN, NEXT, IDENT, HAS_PAIR, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT, EXT, INDENT>(
+  step_body<KEY>(
       A, bt, box, tt, S, s_tab, s_bt, S.tag, S.ranks, S.draws, S.vx, S.vy, S.vz, fx, fy, fz, pos_next, xhold, S.dtv, S.triggersq, S.check, S.flags,
       S.phase, S.which, e, kev[0], S.gmask, S.nvebit, S.lgbit, S.vperm, S.vxo, S.vyo, S.vzo, S.walls, S.indents);
   if (EF) {
@@ -1360,47 +1356,24 @@ void launch_force(DeviceState &d, const BondTable &bt, const double sl[4], bool 
     }
   }, eflag, (parts & 1) != 0, parts == 1, soft && (parts & 1) != 0);
 }
-// f(k_step<the plan's thirteen template arguments, lazy_v as LAZYV before the last three>, its step_variant_key); false: there
-// is no such instantiation
-template <class F>
-static bool with_step_kernel(const StepPlan &p, bool lazy_v, F &&f) {
-  bool found = false;
-  if (p.indent) {
-    // the indent variants are wall variants with one more flag: enumerated on their own, as the EXT variants below
-    if (!p.wall || !p.pair || p.diag || p.ang || p.ef || p.grp || lazy_v || p.soft || p.ext) return false;
-    with_flags([&](auto L, auto N, auto I, auto W4, auto H) {
-      constexpr int W = W4 ? 4 : 1;
-      if constexpr (step_variant_exists(L, N, I, true, W, false, H, false, false, false, false, true, false, false, true)) {
-        f(k_step<L, N, I, true, W, false, H, false, false, false, false, true, false, false, true>,
-          step_variant_key(L, N, I, true, W, false, H, false, false, false, false, true, false, false, true));
-        found = true;
-      }
-    }, p.langevin, p.next, p.ident, p.lpb == 4, p.ahead);
-    return found;
-  }
-  if (p.ext) {
-    // the EXT variants differ in five flags only; a fourteenth flag in the enumeration below would double what the host
-    // compiler has to expand (2^13 -> 2^14 bodies)
-    if (!p.pair || p.diag || p.ang || p.ef || p.grp || lazy_v || p.wall || p.soft) return false;
-    with_flags([&](auto L, auto N, auto I, auto W4, auto H) {
-      constexpr int W = W4 ? 4 : 1;
-      if constexpr (step_variant_exists(L, N, I, true, W, false, H, false, false, false, false, false, false, true)) {
-        f(k_step<L, N, I, true, W, false, H, false, false, false, false, false, false, true>,
-          step_variant_key(L, N, I, true, W, false, H, false, false, false, false, false, false, true));
-        found = true;
-      }
-    }, p.langevin, p.next, p.ident, p.lpb == 4, p.ahead);
-    return found;
-  }
-  with_flags([&](auto L, auto N, auto I, auto P, auto W4, auto D, auto H, auto G, auto E, auto R, auto Z, auto WL, auto SF) {
-    constexpr int W = W4 ? 4 : 1;
-    if constexpr (step_variant_exists(L, N, I, P, W, D, H, G, E, R, Z, WL, SF)) {
-      f(k_step<L, N, I, P, W, D, H, G, E, R, Z, WL, SF>, step_variant_key(L, N, I, P, W, D, H, G, E, R, Z, WL, SF));
-      found = true;
-    }
-  }, p.langevin, p.next, p.ident, p.pair, p.lpb == 4, p.diag, p.ahead, p.ang, p.ef, p.grp, lazy_v, p.wall, p.soft);
-  return found;
+// The launcher's table: the keys that exist, ascending, and k_step<key> of each at the same index - built at compile time from
+// step_variant_exists, which is therefore the one statement of what is compiled.  step_kernel: the instantiation of a key by
+// binary search, nullptr where there is none
+struct StepKeys { int key[count_step_variants()]; };
+constexpr StepKeys existing_step_keys() {
+  StepKeys t{};
+  for (int key = 0, n = 0; key < STEP_KEY_SPACE; key++) if (step_variant_exists(key)) t.key[n++] = key;
+  return t;
 }
+constexpr StepKeys STEP_KEYS = existing_step_keys();
+using StepKernel = decltype(&k_step<0>);
+template <size_t... I>
+static StepKernel step_kernel(int key, std::index_sequence<I...>) {
+  static const StepKernel kernels[] = {k_step<STEP_KEYS.key[I]>...};
+  const int *at = std::lower_bound(std::begin(STEP_KEYS.key), std::end(STEP_KEYS.key), key);
+  return (at != std::end(STEP_KEYS.key) && *at == key) ? kernels[at - STEP_KEYS.key] : nullptr;
+}
+static StepKernel step_kernel(int key) { return step_kernel(key, std::make_index_sequence<count_step_variants()>{}); }
 // Fills the kernel's argument record from the device state, the plan and the launch's arguments - the one place that does -
 // and launches the instantiation the plan names.  ev_start / ev_stop (sampled launches only) take the kernel's own begin /
 // end timestamps from its dispatch packet, the same clock rocprofv3 --kernel-trace reports
@@ -1446,13 +1419,13 @@ static void launch_step_kernel(DeviceState &d, const StepPlan &p, const ForceArg
   // permuted first.  (a launch that stores nothing - a list overflowed - is undone as a whole: undo_step_swap)
   const bool lazy_v = d.v_pending && takes_pending_v(p, d.dd != 0);
   if (!lazy_v) settle_velocities(d);
-  const bool found = p.fused && with_step_kernel(p, lazy_v, [&](auto kernel, int key) {
-    S.indents = itab;
-    d.step_census[key]++;      // (host memory: the launch census, DeviceState::step_census)
-    hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, S,
-                          d.f[0], d.f[1], d.f[2], d.pos_tmp, d.xhold);
-  });
-  if (!found) throw LammpsError("internal: the step plan names a variant of the step kernel that does not exist");
+  const int key = step_plan_key(p, lazy_v);
+  const StepKernel kernel = p.fused ? step_kernel(key) : nullptr;
+  if (!kernel) throw LammpsError("internal: the step plan names a variant of the step kernel that does not exist");
+  S.indents = itab;
+  d.step_census[key]++;      // (host memory: the launch census, DeviceState::step_census)
+  hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), p.lds_pad, d.stream, ev_start, ev_stop, 0, A, *a.bt, d.box, *a.tt, S,
+                        d.f[0], d.f[1], d.f[2], d.pos_tmp, d.xhold);
   d.step_took_v = lazy_v;
   if (lazy_v) { for (int k = 0; k < 3; k++) std::swap(d.v[k], d.v_tmp[k]); d.v_pending = false; }
 }
@@ -1495,54 +1468,36 @@ void launch_step(DeviceState &d, const StepPlan &p, const StepArgs &a) {
   if (p.next && a.swap_buffers) note_step_swapped(d);
 }
 // test hooks (not part of the reference surface, not declared in include/lammps_le.h): the plan for a request under the
-// environment switches as they stand at this call.  req = langevin, next, ident, pair, angles, thermo, nvebit, lgbit, which,
-// check, cells, walls (StepRequest::walls); out = fused, the plan's first ten template arguments in k_step's order (langevin
-// ... grp), bin, member_ranks, diag_bits, lds_pad, whether the dispatcher of launch_step holds the instantiation the plan names
-// (its own look-up, nothing is launched), then [16] = StepPlan::wall and [17] = the plan takes velocities a rebuild left pending
-static void test_step_plan(int n_owned, int decomposed, const int *req, int walls, int *out, int soft = 0, int *out_soft = nullptr,
-                           int ext = 0, int *out_ext = nullptr, int indents = 0, int *out_indent = nullptr) {
+// environment switches as they stand at this call.  Five exported names, one per layout the request and the answer have had;
+// each reads the first `nreq` numbers of the request (the rest: none) and gets the first `nout` of the answer.
+// req = langevin, next, ident, pair, angles, thermo, nvebit, lgbit, which, check, cells, [11] walls (StepRequest::walls),
+// [12] pair_style soft, [13] fix spring/self | addforce | setforce, [14] indenters (StepRequest::indents)
+// out = fused, langevin, next, ident, pair, lpb, diag, ahead, ang, ef, grp, bin, member_ranks, diag_bits, lds_pad, [15] whether
+// the launcher's table holds the instantiation the plan names (its own look-up, nothing is launched), [16] StepPlan::wall,
+// [17] the plan takes velocities a rebuild left pending, [18] StepPlan::soft, [19] StepPlan::ext, [20] the number of
+// instantiations without the indent variants, [21] StepPlan::indent, [22] the number of instantiations
+static void test_step_plan(int n_owned, int decomposed, const int *req, int nreq, int nout, int *out) {
+  int q[15] = {};
+  std::copy(req, req + nreq, q);
   StepRequest r;
-  r.langevin = req[0]; r.next = req[1]; r.ident = req[2]; r.pair = req[3]; r.angles = req[4]; r.thermo = req[5];
-  r.nvebit = req[6]; r.lgbit = req[7]; r.which = req[8]; r.check = req[9]; r.cells = req[10]; r.walls = walls; r.soft = soft != 0; r.ext = ext != 0; r.indents = indents;
+  r.langevin = q[0]; r.next = q[1]; r.ident = q[2]; r.pair = q[3]; r.angles = q[4]; r.thermo = q[5];
+  r.nvebit = q[6]; r.lgbit = q[7]; r.which = q[8]; r.check = q[9]; r.cells = q[10];
+  r.walls = q[11]; r.soft = q[12] != 0; r.ext = q[13] != 0; r.indents = q[14];
   const StepPlan p = plan_step(n_owned, decomposed != 0, r, StepKnobs());
-  const bool known = p.fused && with_step_kernel(p, false, [](auto, int) {});
-  const int v[18] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
-                     p.diag_bits, (int)p.lds_pad, known, p.wall, takes_pending_v(p, decomposed != 0)};
-  for (int k = 0; k < 18; k++) out[k] = v[k];
-  if (out_soft) *out_soft = p.soft;
-  if (out_ext) *out_ext = p.ext;
-  if (out_indent) *out_indent = p.indent;
+  const bool known = p.fused && step_kernel(step_plan_key(p, false));
+  constexpr int variants = count_step_variants(SK_INDENT), all_variants = count_step_variants();   // (at compile time: the sweeps of the host tests call this a million times)
+  const int v[23] = {p.fused, p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, p.bin, p.member_ranks,
+                     p.diag_bits, (int)p.lds_pad, known, p.wall, takes_pending_v(p, decomposed != 0), p.soft, p.ext, variants,
+                     p.indent, all_variants};
+  std::copy(v, v + nout, out);
 }
-// eleven inputs (no walls), the first 16 outputs
-extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) {
-  int v[18];
-  test_step_plan(n_owned, decomposed, req, 0, v);
-  for (int k = 0; k < 16; k++) out[k] = v[k];
-}
-// twelve inputs, req[11] = walls; all 18 outputs
-extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, const int *req, int *out) {
-  test_step_plan(n_owned, decomposed, req, req[11], out);
-}
-// thirteen inputs, req[11] = walls, req[12] = pair_style soft; the 18 outputs of the hook above, then [18] = StepPlan::soft
-extern "C" void lammps_le_test_step_plan_soft(int n_owned, int decomposed, const int *req, int *out) {
-  test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18);
-}
-
-// fourteen inputs, req[11] = walls, req[12] = pair_style soft, req[13] = fix spring/self | addforce | setforce; the 19 outputs of
-// the hook above, then [19] = StepPlan::ext and [20] = count_step_variants(), the number of instantiations the dispatchers hold
-extern "C" void lammps_le_test_step_plan_ext(int n_owned, int decomposed, const int *req, int *out) {
-  test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19);
-  constexpr int variants = count_step_variants();      // (at compile time: the sweeps of the host tests call this a million times)
-  out[20] = variants;
-}
-// fifteen inputs, req[14] = indenters (StepRequest::indents); the 21 outputs of the hook above, then [21] = StepPlan::indent and
-// [22] = count_all_step_variants(), the number of instantiations with the indent variants
-extern "C" void lammps_le_test_step_plan_indent(int n_owned, int decomposed, const int *req, int *out) {
-  test_step_plan(n_owned, decomposed, req, req[11], out, req[12], out + 18, req[13], out + 19, req[14], out + 21);
-  constexpr int variants = count_step_variants(), all_variants = count_all_step_variants();
-  out[20] = variants;
-  out[22] = all_variants;
-}
+extern "C" void lammps_le_test_step_plan(int n_owned, int decomposed, const int *req, int *out) { test_step_plan(n_owned, decomposed, req, 11, 16, out); }
+extern "C" void lammps_le_test_step_plan_walls(int n_owned, int decomposed, const int *req, int *out) { test_step_plan(n_owned, decomposed, req, 12, 18, out); }
+extern "C" void lammps_le_test_step_plan_soft(int n_owned, int decomposed, const int *req, int *out) { test_step_plan(n_owned, decomposed, req, 13, 19, out); }
+extern "C" void lammps_le_test_step_plan_ext(int n_owned, int decomposed, const int *req, int *out) { test_step_plan(n_owned, decomposed, req, 14, 21, out); }
+extern "C" void lammps_le_test_step_plan_indent(int n_owned, int decomposed, const int *req, int *out) { test_step_plan(n_owned, decomposed, req, 15, 23, out); }
+// 1: the launcher's table holds this key (the look-up launch_step_kernel makes; launches nothing, needs no device)
+extern "C" int lammps_le_test_step_dispatch(int key) { return step_kernel(key) != nullptr; }
 
 // ------------------------------------------------------------------------------------------
 // Angle forces (angle_style harmonic | cosine): AngleHarmonic::compute / AngleCosine::compute (src/MOLECULE/

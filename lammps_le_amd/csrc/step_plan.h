@@ -1,7 +1,8 @@
 // step_plan.h — which instantiation of the fused step kernel (k_step, kernels_md.hip) a time step takes, or that it takes
 // the unfused kernels.  Plain host code without a device in it: Engine::iterate states what it knows about the step
 // (StepRequest), plan_step answers, launch_step launches what the plan says.  The set of instantiations that exist is
-// step_variant_exists (below); tests/test_step_plan_cpu.py holds the two against each other.
+// step_variant_exists (below), a rule on the one integer that names an instantiation; tests/test_step_plan_cpu.py holds the two
+// against each other.
 #pragma once
 #include <cstdlib>
 
@@ -45,7 +46,7 @@ struct StepRequest {
 
 struct StepPlan {
   bool fused = false;        // false: not covered by the step kernel, take the unfused kernels (nothing below means anything)
-  // eleven of the twelve template arguments of k_step (the twelfth, LAZYV, is decided at the launch: takes_pending_v)
+  // the bits of the instantiation's key (step_plan_key) but one: SK_LAZYV is decided at the launch (takes_pending_v)
   bool langevin = false, next = false, ident = false, pair = false;
   int lpb = 1;
   bool diag = false, ahead = false, ang = false, ef = false, grp = false;
@@ -55,7 +56,7 @@ struct StepPlan {
   bool ext = false;          // fix spring/self | addforce | setforce evaluated inside the kernel (forceops_on_bead)
   bool bin = false;          // positions binned by this launch
   bool member_ranks = false; // the draws go by the rank among the members of fix langevin's group, not by the canonical rank
-  int diag_bits = 0;         // != 0: the diagnostic launch <true, true, true, true, 1, DIAG> goes first, with these parts switched off
+  int diag_bits = 0;         // != 0: the diagnostic launch (L N I P DIAG, key 47) goes first, with these parts switched off
   unsigned lds_pad = 0;
   int which = -1, nvebit = 1, lgbit = 1;     // run-time arguments that come with the request
   bool check = false;
@@ -119,62 +120,52 @@ inline StepPlan plan_step(int n_owned, bool decomposed, const StepRequest &r, co
   return p;
 }
 
-// The instantiations of k_step that exist, by its template arguments (what plan_step plans with; implies the
-// static_asserts inside k_step): 24 + 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 153.  To exist is to be compiled and to be held
-// by the dispatcher; it is NOT to be launched: Engine::iterate asks for a plan with next = false on a thermo step only, so
-// 84 of the 177 below are never the answer to a request of the engine ("Launch census"; the launches of a
-// handle are counted by their step_variant_key, tests/test_step_census_cpu.py holds the set that can be launched)
-constexpr bool step_variant_exists(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
-                                   bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false) {
-  if (INDENT) return WALL && P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !SOFT && !EXT && (LPB == 1 || AHEAD);   // fix indent inside the wall variant: L, N, I x three shapes = 24
-  if (EXT) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && !SOFT && (LPB == 1 || AHEAD);   // spring/self, addforce, setforce inside the step: L, N, I x three shapes = 24
-  if (SOFT) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && !WALL && (LPB == 1 || AHEAD);   // pair_style soft inside the step: L, N, I x three shapes = 24
-  if (WALL) return P && !DIAG && !ANG && !EF && !GRP && !LAZYV && (LPB == 1 || AHEAD);   // fix wall/region | indent inside the step: L, N, I x three shapes = 24
-  if (LAZYV) return N && P && LPB == 1 && !DIAG && !AHEAD && !ANG && !EF && !GRP;   // velocities handed over after a rebuild: L, I = 4
-  if (DIAG) return L && N && I && P && LPB == 1 && !AHEAD && !ANG && !EF && !GRP;   // the diagnostic launch: 1
-  if (GRP) return !I && P && LPB == 1 && !AHEAD && !EF;      // fixes on groups, with or without angles: L, N, ANG = 8
-  if (EF) return !N && P && LPB == 1 && !AHEAD && !ANG;      // thermo step in one pass: L, I = 4
-  if (ANG) return P && LPB == 1;                             // angles inside the step: L, N, I, AHEAD = 16
-  return LPB == 1 || AHEAD;                                  // L, N, I, P x {four lanes, one lane ahead, one lane} = 48
-}
-constexpr int count_step_variants() {
-  int c = 0;
-  for (int m = 0; m < 16384; m++)
-    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048, m & 4096, m & 8192);
-  return c;
-}
-static_assert(count_step_variants() == 153, "the set of k_step instantiations changed");
-// ... and with the fifteenth argument, INDENT (fix indent has a flag of its own, so that a wall variant without indenters is
-// the code it was): 153 + 24 = 177
-constexpr int count_all_step_variants() {
-  int c = count_step_variants();
-  for (int m = 0; m < 16384; m++)
-    c += step_variant_exists(m & 1, m & 2, m & 4, m & 8, (m & 16) ? 4 : 1, m & 32, m & 64, m & 128, m & 256, m & 512, m & 1024, m & 2048, m & 4096, m & 8192, true);
-  return c;
-}
-static_assert(count_all_step_variants() == 177, "the set of k_step instantiations changed");
-
-// The launch census (DeviceState::step_census, force_census): one integer per instantiation, made of the fifteen template
-// arguments in the bit order of count_step_variants's m - L 0, N 1, I 2, P 3, LPB == 4 4, DIAG 5, AHEAD 6, ANG 7, EF 8,
-// GRP 9, LAZYV 10, WALL 11, SOFT 12, EXT 13, INDENT 14.
+// The identity of an instantiation of k_step: one integer, the template argument of k_step<KEY> and the key of the launch
+// census (DeviceState::step_census).  The bits are named here and nowhere else; their values are recorded in profiles/ and in
+// the tables of the tests, so they stay.  SK_LPB4: four lanes per bead (StepPlan::lpb == 4), clear: one
+enum StepKeyBit : int {
+  SK_LANGEVIN = 1 << 0, SK_NEXT = 1 << 1, SK_IDENT = 1 << 2, SK_PAIR = 1 << 3, SK_LPB4 = 1 << 4, SK_DIAG = 1 << 5, SK_AHEAD = 1 << 6,
+  SK_ANG = 1 << 7, SK_EF = 1 << 8, SK_GRP = 1 << 9, SK_LAZYV = 1 << 10, SK_WALL = 1 << 11, SK_SOFT = 1 << 12, SK_EXT = 1 << 13,
+  SK_INDENT = 1 << 14
+};
 constexpr int STEP_KEY_BITS = 15, STEP_KEY_SPACE = 1 << STEP_KEY_BITS;
-constexpr int step_variant_key(bool L, bool N, bool I, bool P, int LPB, bool DIAG, bool AHEAD, bool ANG, bool EF, bool GRP,
-                               bool LAZYV = false, bool WALL = false, bool SOFT = false, bool EXT = false, bool INDENT = false) {
-  return (int)L | (int)N << 1 | (int)I << 2 | (int)P << 3 | (int)(LPB == 4) << 4 | (int)DIAG << 5 | (int)AHEAD << 6 | (int)ANG << 7 |
-         (int)EF << 8 | (int)GRP << 9 | (int)LAZYV << 10 | (int)WALL << 11 | (int)SOFT << 12 | (int)EXT << 13 | (int)INDENT << 14;
+// The key of the instantiation a plan names; lazy_v: the launch takes velocities a rebuild left pending (takes_pending_v)
+inline int step_plan_key(const StepPlan &p, bool lazy_v) {
+  return (p.langevin ? SK_LANGEVIN : 0) | (p.next ? SK_NEXT : 0) | (p.ident ? SK_IDENT : 0) | (p.pair ? SK_PAIR : 0) |
+         (p.lpb == 4 ? SK_LPB4 : 0) | (p.diag ? SK_DIAG : 0) | (p.ahead ? SK_AHEAD : 0) | (p.ang ? SK_ANG : 0) | (p.ef ? SK_EF : 0) |
+         (p.grp ? SK_GRP : 0) | (lazy_v ? SK_LAZYV : 0) | (p.wall ? SK_WALL : 0) | (p.soft ? SK_SOFT : 0) | (p.ext ? SK_EXT : 0) |
+         (p.indent ? SK_INDENT : 0);
 }
-// the fifteen arguments of a key, in the order of k_step's template (flags[4] = LPB as 1 | 4)
-constexpr void step_key_decode(int key, int flags[STEP_KEY_BITS]) {
-  for (int b = 0; b < STEP_KEY_BITS; b++) flags[b] = (key >> b) & 1;
-  flags[4] = flags[4] ? 4 : 1;
-}
-constexpr bool step_key_exists(int key) {
+
+// The instantiations of k_step that exist, by key (what plan_step plans with; k_step asserts it of its own KEY):
+// 24 + 24 + 24 + 24 + 4 + 1 + 8 + 4 + 16 + 48 = 177.  To exist is to be compiled and to be held by the launcher's table; it is
+// NOT to be launched: Engine::iterate asks for a plan with next = false on a thermo step only, so 84 of the 177 are never the
+// answer to a request of the engine ("Launch census"; the launches of a handle are counted by key,
+// tests/test_step_census_cpu.py holds the set that can be launched)
+constexpr bool step_variant_exists(int key) {
   if (key < 0 || key >= STEP_KEY_SPACE) return false;
-  int f[STEP_KEY_BITS] = {};
-  step_key_decode(key, f);
-  return step_variant_exists(f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], f[10], f[11], f[12], f[13], f[14]);
+  const auto on = [key](int bits) { return (key & bits) != 0; };      // one of `bits` is set
+  const bool one_lane = !on(SK_LPB4), plain_shape = one_lane || on(SK_AHEAD);   // plain shapes: four lanes ahead, one lane ahead, one lane
+  if (on(SK_INDENT)) return on(SK_WALL) && on(SK_PAIR) && !on(SK_DIAG | SK_ANG | SK_EF | SK_GRP | SK_LAZYV | SK_SOFT | SK_EXT) && plain_shape;   // fix indent inside the wall variant: L, N, I x three shapes = 24
+  if (on(SK_EXT)) return on(SK_PAIR) && !on(SK_DIAG | SK_ANG | SK_EF | SK_GRP | SK_LAZYV | SK_WALL | SK_SOFT) && plain_shape;   // spring/self, addforce, setforce inside the step: L, N, I x three shapes = 24
+  if (on(SK_SOFT)) return on(SK_PAIR) && !on(SK_DIAG | SK_ANG | SK_EF | SK_GRP | SK_LAZYV | SK_WALL) && plain_shape;   // pair_style soft inside the step: L, N, I x three shapes = 24
+  if (on(SK_WALL)) return on(SK_PAIR) && !on(SK_DIAG | SK_ANG | SK_EF | SK_GRP | SK_LAZYV) && plain_shape;   // fix wall/region inside the step: L, N, I x three shapes = 24
+  if (on(SK_LAZYV)) return on(SK_NEXT) && on(SK_PAIR) && one_lane && !on(SK_DIAG | SK_AHEAD | SK_ANG | SK_EF | SK_GRP);   // velocities handed over after a rebuild: L, I = 4
+  if (on(SK_DIAG)) return on(SK_LANGEVIN) && on(SK_NEXT) && on(SK_IDENT) && on(SK_PAIR) && one_lane && !on(SK_AHEAD | SK_ANG | SK_EF | SK_GRP);   // the diagnostic launch: 1
+  if (on(SK_GRP)) return !on(SK_IDENT) && on(SK_PAIR) && one_lane && !on(SK_AHEAD | SK_EF);   // fixes on groups, with or without angles: L, N, ANG = 8
+  if (on(SK_EF)) return !on(SK_NEXT) && on(SK_PAIR) && one_lane && !on(SK_AHEAD | SK_ANG);    // thermo step in one pass: L, I = 4
+  if (on(SK_ANG)) return on(SK_PAIR) && one_lane;                                             // angles inside the step: L, N, I, AHEAD = 16
+  return plain_shape;                                                                         // L, N, I, P x three shapes = 48
 }
-// ... and of k_force<E, P, NOBOND, SOFT> (launch_force): E 0, P 1, NOBOND 2, SOFT 3.  Pairs only and pair_style soft need the
+// how many exist among the keys with none of `without` set.  153 without fix indent's bit (which is a flag of its own so that a
+// wall variant without indenters is the code it was), 177 in all: the test hooks report both
+constexpr int count_step_variants(int without = 0) {
+  int c = 0;
+  for (int key = 0; key < STEP_KEY_SPACE; key++) c += !(key & without) && step_variant_exists(key);
+  return c;
+}
+static_assert(count_step_variants(SK_INDENT) == 153 && count_step_variants() == 177, "the set of k_step instantiations changed");
+// The census key of k_force<E, P, NOBOND, SOFT> (launch_force, DeviceState::force_census): E 0, P 1, NOBOND 2, SOFT 3.  Pairs only and pair_style soft need the
 // pair part: 8 + 2 = 10 instantiations
 constexpr int FORCE_KEY_BITS = 4, FORCE_KEY_SPACE = 1 << FORCE_KEY_BITS;
 constexpr bool force_variant_exists(bool E, bool P, bool NOBOND, bool SOFT) { return (void)E, (P || !NOBOND) && (P || !SOFT); }
@@ -187,8 +178,7 @@ constexpr bool force_key_exists(int key) {
 // of the kernel, in one launch over every bead of one GPU, with no diagnostic launch in front of it.  Engine::iterate asks
 // before it lets a rebuild leave them, launch_step when it picks the instantiation.
 inline bool takes_pending_v(const StepPlan &p, bool decomposed) {
-  return p.fused && step_variant_exists(p.langevin, p.next, p.ident, p.pair, p.lpb, p.diag, p.ahead, p.ang, p.ef, p.grp, true, p.wall, p.soft, p.ext, p.indent) &&
-         p.which < 0 && !p.diag_bits && !decomposed;
+  return p.fused && step_variant_exists(step_plan_key(p, true)) && p.which < 0 && !p.diag_bits && !decomposed;
 }
 
 }  // namespace lmp_le

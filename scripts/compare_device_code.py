@@ -2,7 +2,11 @@
 (hipcc <the Makefile's CXXFLAGS> --cuda-device-only -c kernels_md.hip -o X.o) per kernel symbol: the same set of names,
 and for each name the same code bytes and the same kernel descriptor.  Symbol order may differ between the builds, so the
 descriptor's entry offset (bytes 16..23: the distance from the descriptor to the code) is left out of the comparison.
-usage: compare_device_code.py [--renamed] BEFORE.o AFTER.o      (no GPU needed; exit status 1 on any difference)
+usage: compare_device_code.py [--renamed | --step-keys] BEFORE.o AFTER.o      (no GPU needed; exit status 1 on any difference)
+--step-keys: for the change of k_step's fifteen template arguments into one key - every k_step<fifteen arguments> of the first
+object is paired BY NAME with k_step<the key of those arguments> of the second and must have the same code bytes and the same
+whole descriptor; a kernel of either object that is left without a partner fails.  (--renamed accepts any twin; this pins the
+bit order.)
 --renamed: for a change that adds template or kernel arguments to a kernel, which renames every instantiation - a kernel whose
 name is in the first object only passes if some kernel whose name is in the second object only has the same code bytes and
 the same descriptor but for its kernarg size (bytes 8..11).  Kernels in both objects are compared by name as always."""
@@ -43,8 +47,22 @@ def kernels(obj):
     return out
 
 
+def step_key(symbol):
+    """The key of a k_step symbol: k_step<KEY> names it; of k_step<L, N, I, P, LPB, ...> - fifteen arguments - it is argument b
+    as bit b, the lanes per bead (argument 4, 1 | 4) as `== 4` (csrc/step_plan.h, StepKeyBit).  None: not a k_step symbol."""
+    m = re.search(r"6k_stepI((?:L[bi]\d+E)+)E", symbol)
+    if not m:
+        return None
+    v = [int(x) for x in re.findall(r"L[bi](\d+)E", m.group(1))]
+    if len(v) == 1:
+        return v[0]
+    assert len(v) == 15 and v[4] in (1, 4), symbol
+    return sum((x == 4 if b == 4 else x != 0) << b for b, x in enumerate(v))
+
+
 renamed = "--renamed" in sys.argv[1:]
-args = [x for x in sys.argv[1:] if x != "--renamed"]
+step_keys = "--step-keys" in sys.argv[1:]
+args = [x for x in sys.argv[1:] if x not in ("--renamed", "--step-keys")]
 a, b = kernels(args[0]), kernels(args[1])
 ka = {n for n in a if n + ".kd" in a}
 kb = {n for n in b if n + ".kd" in b}
@@ -60,4 +78,13 @@ if renamed:
     print("renamed: %d kernels of the first object only, %d of the second only; of the first, without a twin in code and descriptor: %d"
           % (len(ka - kb), len(kb - ka), len(lost)), lost[:5])
     sys.exit(1 if diff or lost else 0)
+if step_keys:
+    old = {n: step_key(n) for n in ka - kb}
+    new = {step_key(n): n for n in kb - ka}
+    unpaired = sorted(n for n, k in old.items() if k is None or k not in new) + sorted(n for k, n in new.items() if k is None or k not in old.values())
+    pairs = [(n, new[k]) for n, k in sorted(old.items()) if k in new and k is not None]
+    differ = [(n, m) for n, m in pairs if a[n] != b[m] or a[n + ".kd"] != b[m + ".kd"]]
+    print("step keys: %d pairs k_step<fifteen arguments> / k_step<key>, differences in code or descriptor: %d, unpaired: %d"
+          % (len(pairs), len(differ), len(unpaired)), differ[:3], unpaired[:5])
+    sys.exit(1 if diff or differ or unpaired or len(old) != len(new) else 0)
 sys.exit(1 if diff or ka != kb else 0)

@@ -1,5 +1,5 @@
-"""The launch census of the step kernel for the tests: the key of an instantiation (csrc/step_plan.h step_variant_key,
-force_variant_key) restated in Python, the engine's test hooks around it, and LIVE - the keys Engine::iterate can launch,
+"""The launch census of the step kernel for the tests: the key of an instantiation (csrc/step_plan.h StepKeyBit - the template
+argument of k_step<KEY> -, force_variant_key) restated in Python, the engine's test hooks around it, and LIVE - the keys Engine::iterate can launch,
 from a model of the requests it makes swept through the planner (lammps_le_test_step_plan_indent; nothing is launched)."""
 import ctypes
 import functools
@@ -9,7 +9,7 @@ import os
 from test_step_plan_cpu import KNOBS, NAMES, SIZES
 
 STEP, FORCE = 0, 1
-# k_step's fifteen template arguments in the template's order = the key's bit order (LPB: 1 | 4, bit 4 set for 4)
+# the fifteen flags of k_step<KEY> in the key's bit order (csrc/step_plan.h StepKeyBit; LPB: lanes per bead, 1 | 4, bit 4 set for 4)
 FLAGS = ("L", "N", "I", "P", "LPB", "DIAG", "AHEAD", "ANG", "EF", "GRP", "LAZYV", "WALL", "SOFT", "EXT", "INDENT")
 FORCE_FLAGS = ("E", "P", "NOBOND", "SOFT")
 
@@ -25,7 +25,7 @@ def force_key(E=0, P=0, NOBOND=0, SOFT=0):
 
 
 def flags(k):
-    """key -> the fifteen template arguments as a tuple of ints"""
+    """key -> the fifteen flags as a tuple of ints"""
     return tuple((4 if (k >> 4) & 1 else 1) if b == 4 else (k >> b) & 1 for b in range(15))
 
 
@@ -56,6 +56,8 @@ def lib():
     L.lammps_le_test_step_key_decode.restype = None
     L.lammps_le_test_step_key.argtypes = [ctypes.c_int, PI]
     L.lammps_le_test_step_key.restype = ctypes.c_int
+    L.lammps_le_test_step_dispatch.argtypes = [ctypes.c_int]
+    L.lammps_le_test_step_dispatch.restype = ctypes.c_int
     L.lammps_le_test_step_plan_indent.argtypes = [ctypes.c_int, ctypes.c_int, PI, PI]
     L.lammps_le_test_step_plan_indent.restype = None
     return L
@@ -68,6 +70,11 @@ def existing_keys(kernel=STEP):
     n = lib().lammps_le_test_step_keys(kernel, cap, buf)
     assert n <= cap
     return list(buf[:n])
+
+
+def dispatched(k):
+    """1: the launcher's table holds k_step<k> (its own look-up; nothing is launched, no device)"""
+    return lib().lammps_le_test_step_dispatch(k)
 
 
 def engine_key(f, kernel=STEP):
@@ -134,7 +141,7 @@ def launched_by(out):
     # takes_pending_v holds (out[17])
     if out[17]:
         got.add(key(LAZYV=1, **args))
-    # launch_step: `if (p.diag_bits)` the instantiation <true, true, true, true, 1, DIAG> goes first; plan_step sets diag_bits
+    # launch_step: `if (p.diag_bits)` the instantiation L N I P DIAG (key 47) goes first; plan_step sets diag_bits
     # from StepKnobs::diag_step = LAMMPS_LE_DIAG_STEP alone
     if out[13]:
         got.add(key(L=1, N=1, I=1, P=1, DIAG=1))
@@ -169,3 +176,10 @@ def live_keys():
             os.environ.pop(k, None)
         os.environ.update(saved)
     return frozenset(live)
+
+
+if __name__ == "__main__":
+    # python tests/step_census.py 1039 47 ...: the flags of the k_step<KEY> a kernel trace or a census file shows
+    import sys
+    for arg in sys.argv[1:]:
+        print(names([int(arg)]))

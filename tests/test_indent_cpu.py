@@ -195,12 +195,12 @@ def _hook(name, nreq, nout):
 
 @pytest.mark.parametrize("env", [{}, {"LAMMPS_LE_LPB": "1"}, {"LAMMPS_LE_LPB": "1", "LAMMPS_LE_AHEAD_MAX_N": "0"}, {"LAMMPS_LE_NO_FUSE": "1"}])
 def test_step_plan_with_indenters(monkeypatch, env):
-    """Fix indent has a template flag of its own, so that a wall variant without indenters stays the code it was.  indents = 1
+    """Fix indent has a bit of the kernel's key of its own, so that a wall variant without indenters stays the code it was.  indents = 1
     gives, request by request, the plan walls = 1 gives (so it fuses in exactly the shapes walls = 1 does) with StepPlan::indent
     set on top, alone and together with walls = 1, and the dispatcher holds the instantiation; indents = 2, and indents = 1
     beside walls = 2, never fuse; thermo steps, angle styles, pair_style soft and the force fixes do not fuse with an indenter;
-    without indenters the hook answers as the one before it and no plan has the flag.  The instantiations over the fourteen
-    flags there were are still 153; with the 24 indent variants (L, N, I x three shapes) there are 177."""
+    without indenters the hook answers as the one before it and no plan has the flag.  The instantiations without that
+    bit are still 153; with the 24 indent variants (L, N, I x three shapes) there are 177."""
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():

@@ -1,4 +1,4 @@
-"""The launch census of the step kernel without a device: the key of an instantiation (csrc/step_plan.h step_variant_key,
+"""The launch census of the step kernel without a device: the key of an instantiation (csrc/step_plan.h StepKeyBit,
 force_variant_key through the engine's test hooks), the set of instantiations Engine::iterate can launch (LIVE) and the set it
 cannot (DORMANT) against literal tables, and the closing condition on the GPU matrix: the rows of
 test_gpu_step_census.CASES, taken together, name every live instantiation - over the table, not over what happened to run.
@@ -17,7 +17,7 @@ import pytest
 import step_census as sc
 import test_step_plan_cpu as tp
 
-# k_step's template arguments: L, N, I, P, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT, EXT, INDENT
+# the flags of k_step<KEY> in the key's bit order: L, N, I, P, LPB, DIAG, AHEAD, ANG, EF, GRP, LAZYV, WALL, SOFT, EXT, INDENT
 LIVE = {
     # base: 24
     (0, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0), (1, 1, 0, 0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0),
@@ -140,7 +140,7 @@ FORCE_DORMANT = {(1, 1, 1, 0), (1, 1, 1, 1)}
 
 def test_key_function():
     """The key is a bijection on the 177 + 10 instantiations, decode and key are inverse to each other (the engine's and the
-    restatement of step_census.py alike), the bit order is that of count_step_variants: LPB = 4 bit 4, LAZYV bit 10, INDENT
+    restatement of step_census.py alike), the bit order is that of StepKeyBit: LPB = 4 bit 4, LAZYV bit 10, INDENT
     bit 14; the enumeration agrees with the rule of test_step_plan_cpu.exists on the ten-argument subset."""
     keys, fkeys = sc.existing_keys(sc.STEP), sc.existing_keys(sc.FORCE)
     assert len(keys) == len(set(keys)) == 177 and len(fkeys) == len(set(fkeys)) == 10
@@ -164,6 +164,17 @@ def test_key_function():
     assert ten == want and len(ten) == 77
     # a key that is no instantiation decodes, and is not enumerated
     assert sc.key(L=1, N=1, LAZYV=1, WALL=1) not in keys
+
+
+def test_dispatch_table_holds_the_existing_keys():
+    """The launcher's table (kernels_md.hip step_kernel, through lammps_le_test_step_dispatch: its own look-up, nothing is
+    launched) holds a key of the whole key space exactly where the rule says the instantiation exists: 177 keys."""
+    existing = set(sc.existing_keys())
+    answers = [sc.dispatched(k) for k in range(1 << 15)]
+    wrong = [k for k, held in enumerate(answers) if held != (1 if k in existing else 0)]
+    assert not wrong, sc.names(wrong)
+    assert sum(answers) == len(existing) == 177
+    assert sc.dispatched(-1) == 0 and sc.dispatched(1 << 15) == 0
 
 
 def test_live_and_dormant_tables():

@@ -35,7 +35,7 @@ def _hook():
 
 
 def expected(n, dd, r, env):
-    """The rules of the step kernel's choice: (the first ten of k_step's twelve template arguments, bin, draws by the
+    """The rules of the step kernel's choice: (the first ten flags of k_step's key in its bit order, bin, draws by the
     member-rank table, bits of the diagnostic pre-launch, LDS pad) or UNFUSED."""
     L, N, I, P, angles, thermo, nvebit, lgbit, which, check, cells = r
     L, N, I, P = bool(L), bool(N), bool(I), bool(P)
@@ -71,7 +71,7 @@ def expected(n, dd, r, env):
 
 
 def exists(L, N, I, P, LPB, DIAG, AHEAD, ANG, EF, GRP):
-    """The rule of csrc/step_plan.h step_variant_exists, restated for the ten template arguments a request without walls
+    """The rule of csrc/step_plan.h step_variant_exists, restated for the ten flags of the key a request without walls
     decides (LAZYV and WALL false): 77 of k_step's 105 instantiations - 16 * 3 + 8 * 2 + 4 + 8 + 1.  The other 28 are the
     four that take the velocities a rebuild left pending (tests/test_lazy_permute_cpu.py) and the 24 of fix wall/region
     (tests/test_wall_cpu.py)."""
